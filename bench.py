@@ -7,7 +7,23 @@ Loss -> backward -> clip(2.0) + Adam; when n>1 the optimizer is sharded
 bf16 compute, dropout 0.3 on, synthetic seeded inputs of the reference shapes
 (features [B,T,256] f32, targets [B,T,61] f32, already resident in HBM).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up, W
+warm-up steps, K timed steps, the `--dump-outputs` files, one JSON line
+(`value` = frames/s, `ms_per_step` = milliseconds per timed step).  `roofline`
+in a plain line is the in-step part only: HIP events around the GEMM launches of
+the last timed step, as before.  Every measurement that takes a run of its own
+is behind `--full`: the rocprofv3 counter passes (`roofline.traffic`,
+`mfma_busy`), `feature_inclusive`, `data_feed`, `parity` and `cpu_baseline`;
+with `--full` the flags that switch single legs off (--no-traffic,
+--no-cpu-baseline, --no-parity, --feature-steps 0, --feed-steps 0) apply.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step
+handed its caller as float32 `DIR/<name>.npy` (dump_outputs): the loss, the
+prediction, the clip norm, and fixed seeded samples of the gradients and of the
+updated weights.  Weights, inputs and dropout seeds are seeded, so two builds
+run with the same arguments can be compared array for array.
 
 N>1: started as `python bench.py --gpus N`, this process touches no GPU and
 runs `python -m torch.distributed.run --nnodes 1 --nproc-per-node N
@@ -118,8 +134,7 @@ def measure_gemm_counters(args):
         d = tempfile.mkdtemp(prefix="nstl_pmc_", dir="/tmp")
         cmd = ["timeout", "-s", "KILL", "240", exe, "--pmc"] + counters + [
                "-d", d, "-o", "run", "--output-format", "csv",
-               "--", sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-               "--no-parity", "--feature-steps", "0", "--feed-steps", "0", "--no-traffic",
+               "--", sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1",  # a plain run
                "--batch", str(args.batch), "--seq", str(args.seq)] + (["--fp8"] if args.fp8 else []) + \
               (["--fp8-bwd"] if args.fp8_bwd else [])
         env = dict(os.environ, TMPDIR="/tmp")
@@ -375,6 +390,46 @@ def fwd_parity(cfg, dev, T, windows=2):
     return out
 
 
+DUMP_MAX_ELEMS = 4 << 20    # the prediction: whole up to 16 MB of float32, sampled beyond
+DUMP_ARENA_ELEMS = 2 << 20  # sampled elements of the gradient and weight arenas (228M each): 8 MB each
+
+
+def _dump_array(t, max_elems, seed):
+    """t as a float32 numpy array: whole if it has at most max_elems elements,
+    else its elements at max_elems sorted positions drawn with replacement by a
+    generator of its own (the same positions in every run; the global RNG, which
+    draws the dropout seeds, is not advanced)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > max_elems:
+        idx = torch.randint(0, flat.numel(), (max_elems,), generator=torch.Generator().manual_seed(seed))
+        flat = flat.index_select(0, idx.sort().values.to(flat.device))
+        return flat.float().cpu().numpy()
+    return flat.float().cpu().numpy().reshape(tuple(t.shape))
+
+
+def dump_outputs(path, loss, pred, opt, eng):
+    """--dump-outputs: what the last timed step handed its caller, as float32
+    DIR/<name>.npy (under 64 MB in all):
+      loss        [1]        the step's loss
+      pred        [B, T, 61] the model's output for the step's batch
+      grad_norm   [1]        the global gradient norm the clip used
+      grads       [2M]       the gradient arena (every p.grad, unclipped), sampled
+      params      [2M]       the weights after the update, sampled: the f32 master
+                             arena, or the compute-dtype arena where a sharded
+                             optimizer leaves the master stale outside the shard
+    The samples are the same seeded positions of the flat arenas in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    eng.sync_pending()  # the queued update of the last step
+    torch.cuda.synchronize()
+    arrays = {"loss": loss.reshape(1), "pred": pred, "grad_norm": opt.last_norm.reshape(1),
+              "grads": eng.g32, "params": eng.p16 if eng.master_stale else eng.p32}
+    for name, t in arrays.items():
+        n_max = DUMP_ARENA_ELEMS if name in ("grads", "params") else DUMP_MAX_ELEMS
+        np.save(os.path.join(path, name + ".npy"), _dump_array(t, n_max, 77))
+    log("--dump-outputs: %s in %s" % (", ".join(n + ".npy" for n in arrays), path))
+
+
 def rank_launch_cmd(args, argv, port):
     """The torch.distributed.run command that starts args.gpus ranks of this
     bench on one node (the form the reference's ≤4-replica loop becomes: one
@@ -515,6 +570,12 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--seq", type=int, default=128)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as float32 DIR/<name>.npy "
+                         "(loss, pred, grad_norm, seeded samples of grads and params; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement that takes a run of its own: rocprofv3 counter passes, "
+                         "feature-inclusive and data-feed variants, forward parity, CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the forward-MSE-vs-oracle field")
     ap.add_argument("--gemm-sample-steps", type=int, default=1,
@@ -538,6 +599,11 @@ def main(argv=None):
     ap.add_argument("--launch-limit-s", type=float, default=1500.0,
                     help="--gpus N self-launch: an attempt running longer than this is stopped")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the timed steps only
+        args.no_traffic = args.no_parity = args.no_cpu_baseline = True
+        args.feature_steps = args.feed_steps = 0
 
     env_world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if env_world == 0 and args.gpus > 1:
@@ -554,7 +620,7 @@ def main(argv=None):
     from neurosync_trainer_lite_amd.utils.training_utils import gradient_exchange
 
     # PMC traffic passes first: child processes, started before this one touches the GPU
-    traffic, traffic_src, mfma_busy = None, "skipped (--no-traffic or n>1)", None
+    traffic, traffic_src, mfma_busy = None, "skipped (measured with --full, without --no-traffic, n = 1)", None
     counters = {}
     if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_traffic:
         counters = measure_gemm_counters(args)
@@ -590,9 +656,16 @@ def main(argv=None):
     # update MAY run under it -- only with NSTL_ADAM_OVERLAP=1 (FusedAdam: opt-in)
     opt.overlap_next_forward = True
 
+    # --dump-outputs: a copy of the model's output, taken in the last timed step only
+    # (the output is a view of engine workspace that later kernels may reuse)
+    keep_pred, kept_pred = [False], [None]
+
     def step(x=src, y=trg):
         opt.zero_grad()
-        loss = crit(model(x), y)
+        pred = model(x)
+        if keep_pred[0]:
+            kept_pred[0] = pred.detach().clone()
+        loss = crit(pred, y)
         loss.backward()
         opt.step(max_norm=2.0)
         return loss
@@ -682,6 +755,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     for i in range(args.steps):
         sample[0] = i >= args.steps - args.gemm_sample_steps
+        keep_pred[0] = args.dump_outputs is not None and i == args.steps - 1
         loss = step()
     torch.cuda.synchronize()
     if world > 1:
@@ -701,6 +775,9 @@ def main(argv=None):
     loss_v = loss.item()
     if not (loss_v == loss_v):
         raise RuntimeError("non-finite loss %r" % loss_v)
+    keep_pred[0] = False
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, loss, kept_pred[0], opt, eng)
 
     # bf16 launches -> `roofline` (vs the bf16 peak); fp8 launches (--fp8) -> `roofline_fp8`
     ev16 = [e for e in gemm_events if not e[4]]
@@ -866,6 +943,7 @@ def main(argv=None):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_step, 3),
             "higher_is_better": True,
             "scaling": "weak",

@@ -1,4 +1,4 @@
-# round-end evidence on one box: the whole GPU suite, smoke(), the default bench
+# round-end evidence on one box: the whole GPU suite, smoke(), the bench --full
 # line (with its PMC traffic passes and CPU baseline), and a kernel-trace profile
 #   tools/run_final.sh <tag>
 set -o pipefail
@@ -9,8 +9,10 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 gpurun_out/${TAG}_gpu_tests.txt
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.txt 2>&1 || { tail -20 gpurun_out/${TAG}_smoke.txt; exit 1; }
 tail -2 gpurun_out/${TAG}_smoke.txt
-timeout -k 10 900 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { tail -20 gpurun_out/${TAG}_bench.err; exit 1; }
-cat gpurun_out/${TAG}_bench.json | cut -c1-600
+BENCH=${NSTL_BENCH_OUT:-bench_out}/${TAG}_bench  # the --full line: counters, variants, parity, CPU baseline
+mkdir -p $(dirname $BENCH)
+timeout -k 10 900 python bench.py --full > $BENCH.json 2> $BENCH.err || { tail -20 $BENCH.err; exit 1; }
+cut -c1-600 $BENCH.json
 fi
 [ "${2:-all}" = "tests" ] && exit 0
 bash tools/run_prof_step.sh ${TAG}_prof > /dev/null 2>&1 || { echo "profile failed"; exit 1; }

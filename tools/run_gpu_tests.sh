@@ -10,5 +10,7 @@ tail -25 gpurun_out/${TAG}_gpu_tests.txt
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.txt 2>&1 || { tail -20 gpurun_out/${TAG}_smoke.txt; exit 1; }
 tail -1 gpurun_out/${TAG}_smoke.txt
-timeout -k 10 900 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { tail -20 gpurun_out/${TAG}_bench.err; exit 1; }
-cut -c1-700 gpurun_out/${TAG}_bench.json
+BENCH=${NSTL_BENCH_OUT:-bench_out}/${TAG}_bench  # the --full line: counters, variants, parity, CPU baseline
+mkdir -p $(dirname $BENCH)
+timeout -k 10 900 python bench.py --full > $BENCH.json 2> $BENCH.err || { tail -20 $BENCH.err; exit 1; }
+cut -c1-700 $BENCH.json

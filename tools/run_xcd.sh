@@ -6,8 +6,10 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method threa
 grep -E "passed|failed" gpurun_out/xcd_tests.log | tail -2
 bash tools/ab_lib.sh 2 || exit 1
 bash tools/ab_lib.sh 1 "old new" || exit 1
-timeout -k 10 600 python bench.py --no-cpu-baseline --no-parity --feature-steps 0 --feed-steps 0 > gpurun_out/xcd_bench.json 2> gpurun_out/xcd_bench.err || { tail -5 gpurun_out/xcd_bench.err; exit 1; }
+BENCH=${NSTL_BENCH_OUT:-bench_out}/xcd_bench  # --full for the counter passes (traffic per family)
+mkdir -p $(dirname $BENCH)
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-parity --feature-steps 0 --feed-steps 0 > $BENCH.json 2> $BENCH.err || { tail -5 $BENCH.err; exit 1; }
 python -c "
-import json; d=json.load(open('gpurun_out/xcd_bench.json')); r=d['roofline']
+import json; d=json.load(open('$BENCH.json')); r=d['roofline']
 print('value', d['value'], 'traffic_vs_alg', r.get('traffic_vs_algorithmic'))
 for k,v in r['by_family'].items(): print(k, v['avg_launch_us'], v['frac'], v.get('traffic_vs_algorithmic'))"
