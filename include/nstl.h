@@ -125,7 +125,15 @@ int nstl_fp8_quant_cols(int x_dtype, const nstl_fp8_job* jobs, int n, void* stre
  * (by the projection epilogue), softmax scale 1/sqrt(dh), attention-probability
  * dropout.  Replaces F.scaled_dot_product_attention at utils/model.py:126-127.
  * Element (b,t,h,d) of X lives at X[(b*T + t)*X_ld + h*dh + d].
- * Constraints: dh == 64; T % 16 == 0; T <= 256 (bf16) / 128 (f32). */
+ * Three kernel families, chosen per call (same scale, LSE, dropout stream and
+ * RoPE^T conventions, so they are interchangeable):
+ *   one-shot MFMA : dh == 64, T % 32 == 0, T <= 256 (bf16) / 128 (f32); a head's
+ *                   whole K / V in LDS, a query's score row in registers;
+ *   streaming MFMA: dh == 64, bf16, T % 32 == 0, 256 < T <= 4096; key / query
+ *                   tiles through LDS, online softmax (NSTL_ATTN_LONG=0: off);
+ *   generic       : everything else with dh % 8 == 0, dh <= 512, T <= 4096 (f32
+ *                   past T = 128, ragged T, other head sizes): one wave per row,
+ *                   no MFMA; a correctness path, not a training path. */
 typedef struct nstl_attn_args {
   int dtype;
   int B, T, H, dh;
@@ -220,7 +228,9 @@ int nstl_rope(int in_dtype, const void* in, int64_t in_ld, int out_dtype, void* 
               int inverse, int accumulate, void* stream);
 
 /* Fused Loss forward + backward.  Replaces Loss.forward (utils/model.py:278-291)
- * and its autograd backward.  loss_out[0..3] = total, rec, temp, dir. */
+ * and its autograd backward.  loss_out[0..3] = total, rec, temp, dir.
+ * 2 <= T <= 4096, F <= 64: clips up to 256 frames are staged whole in LDS, longer
+ * ones in time chunks with one frame of halo (same sums, same normalisers). */
 typedef struct nstl_loss_args {
   int B, T, F;
   const float* pred; int64_t pred_ld;
@@ -353,6 +363,8 @@ enum {
   NSTL_K_GEMM4_SK,           /*   ... launches with a stream-K tail (grid not dividing the tiles) */
   NSTL_K_GEMM_FP8_ROPE,      /* fp8 GEMM launches with the RoPE epilogue (C5 q|k|v, cross q, cross k|v) */
   NSTL_K_GEMM4F8,            /* fp8 GEMM launches on the 4-wave persistent kernel (the rest: NSTL_K_GEMM_FP8) */
+  NSTL_K_ATTN_FWD_LONG,      /* streaming MFMA attention forward (bf16, 256 < T <= 4096) */
+  NSTL_K_ATTN_BWD_LONG,      /*   ... its backward (dQ + dK/dV kernel pair) */
   NSTL_K_COUNT
 };
 /* Copy-engine ZeRO-1 (parallel.ShardPusher; replaces the reference's gather of

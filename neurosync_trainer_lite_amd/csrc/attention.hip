@@ -3,7 +3,8 @@
 // autograd backward; RoPE (apply_rope_qk, :60-83) is applied to q/k by the
 // projection epilogue, and rotated back here on dq/dk).
 //
-// Shapes are short: T <= 256 frames, dh = 64.  A whole (batch, head) key/value
+// Shapes are short: T <= 256 frames, dh = 64 (longer bf16 windows take the streaming
+// kernels of attention_long.hip).  A whole (batch, head) key/value
 // sequence fits in LDS, so there is no online softmax and no cross-workgroup
 // reduction:
 //   forward : workgroup = (b, h, 128 queries); each wave 16 queries; scores for
@@ -19,6 +20,7 @@
 #include <algorithm>
 
 #include "../../include/nstl.h"
+#include "attention_long.h"
 #include "common.h"
 #include "status.h"
 
@@ -1537,8 +1539,9 @@ int fill(AttnParams& p, const nstl_attn_args* a, bool bwd) {
                        ((uintptr_t)a->dq | (uintptr_t)a->dk | (uintptr_t)a->dv) % 16 == 0,
                    "nstl_attn_bwd: dq/dk/dv must be 16-byte aligned");
     NSTL_CHECK_ARG(!(a->rope_q || a->rope_k) || (a->rope_cos && a->rope_sin), "nstl_attn_bwd: rope tables");
-    NSTL_CHECK_ARG(!use_fast(a) || a->dsum, "nstl_attn_bwd: dsum scratch [B*H*T] f32 missing");
-    NSTL_CHECK_ARG(!a->dbias_part || use_fast(a), "nstl_attn_bwd: dbias_part needs the MFMA path (head_dim 64)");
+    const bool mfma = use_fast(a) || nstl::attn_long_takes(a);
+    NSTL_CHECK_ARG(!mfma || a->dsum, "nstl_attn_bwd: dsum scratch [B*H*T] f32 missing");
+    NSTL_CHECK_ARG(!a->dbias_part || mfma, "nstl_attn_bwd: dbias_part needs the MFMA path (head_dim 64)");
   }
   p.q = (const char*)a->q; p.q_ld = a->q_ld;
   p.k = (const char*)a->k; p.k_ld = a->k_ld;
@@ -1604,6 +1607,7 @@ extern "C" int nstl_attn_fwd(const nstl_attn_args* a, void* stream) {
   if (rc) return rc;
   const int esz = a->dtype == NSTL_F32 ? 4 : 2;
   hipStream_t st = (hipStream_t)stream;
+  if (nstl::attn_long_takes(a)) return nstl::attn_long_fwd(a, st);  // bf16, 256 < T: streaming kernels
   if (!use_fast(a)) {
     nstl::count(NSTL_K_ATTN_FWD_GENERIC);
     dim3 grid((a->T + 3) / 4, a->B * a->H);
@@ -1644,6 +1648,7 @@ extern "C" int nstl_attn_bwd(const nstl_attn_args* a, void* stream) {
   if (rc) return rc;
   const int esz = a->dtype == NSTL_F32 ? 4 : 2;
   hipStream_t st = (hipStream_t)stream;
+  if (nstl::attn_long_takes(a)) return nstl::attn_long_bwd(a, p.rope_fast, st);
   if (!use_fast(a)) {
     nstl::count(NSTL_K_ATTN_BWD_GENERIC);
     dim3 grid((a->T + 3) / 4, a->B * a->H);
@@ -1687,6 +1692,6 @@ extern "C" int nstl_attn_bwd(const nstl_attn_args* a, void* stream) {
 }
 
 extern "C" int nstl_attn_bias_rows(const nstl_attn_args* a) {
-  if (a == nullptr || !use_fast(a)) return 0;
+  if (a == nullptr || !(use_fast(a) || nstl::attn_long_takes(a))) return 0;
   return a->B * ((a->T + BWD_ROWS - 1) / BWD_ROWS);
 }

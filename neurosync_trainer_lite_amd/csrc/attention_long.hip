@@ -1,0 +1,746 @@
+// Streaming MFMA attention for long windows (bf16, head_dim 64, T % 32 == 0,
+// 256 < T <= 4096): the shapes past the one-shot kernels of attention.hip, whose
+// score rows live in registers and whose K / V of a whole head live in LDS.
+//
+// Here nothing of size T x T or T per lane is held.  Every kernel owns a block of
+// 128 rows of one (batch, head) -- 8 waves, 16 rows each, the wave's own rows
+// loaded from global memory straight into MFMA fragments -- and walks the other
+// sequence index in tiles of 64 rows that go through LDS by LDS-DMA, two
+// buffers: tile t+1 is in flight while tile t is computed.
+//   forward : 128 queries; K / V tiles; S^T = K Q^T per tile, online softmax
+//             (running max and running sum per query in f32, O accumulators
+//             rescaled when the max moves), O += V^T P^T from the score registers.
+//   dQ      : 128 queries; K / V tiles; P recomputed from the saved LSE;
+//             also writes D = rowsum(dO * O).
+//   dK / dV : 128 keys; Q / dO tiles; accumulators in registers over the sweep.
+// No atomics on global memory and no cross-workgroup sums: every output element
+// has one writer and a fixed summation order.
+// Conventions (scale, LSE, dropout on the normalised probabilities, the
+// nstl_keep(seed, drop_idx) stream, RoPE^T on dq / dk, bias partial rows) are
+// those of attention.hip, so the paths are interchangeable.  The operand images,
+// fragment orders and epilogue helpers below are the bf16 forms of that file's.
+//
+// Tails: T % 32 == 0, so a wave's 16 rows are all in range or all out, and a
+// tile holds 64 or (the last one) 32 valid rows.  The backward kernels only
+// touch a tile's valid 32-row chunks.  The forward computes the whole tile: its
+// DMA clamps the row index to T - 1 (nothing is read past the head's T rows) and
+// the out-of-range scores are set to -inf, i.e. probability exactly 0.
+#include <stdlib.h>
+
+#include "../../include/nstl.h"
+#include "attention_long.h"
+#include "common.h"
+#include "status.h"
+
+namespace {
+
+constexpr int DH = 64;
+constexpr int LNT = 512, NW = LNT / 64, ROWS = 16 * NW;  // 8 waves, 128 rows per workgroup
+constexpr int KT = 64;                                    // streamed rows per tile
+constexpr int TILE_B = KT * DH * 2, BUF_B = 2 * TILE_B;   // one image 8 KB; a buffer holds two
+constexpr int LONG_MIN_T = 256, LONG_MAX_T = 4096;        // (one-shot limit, T range of nstl_attn]
+constexpr float LOG2E = 1.4426950408889634f;
+
+struct LongParams {
+  const char* q; int64_t q_ld;
+  const char* k; int64_t k_ld;
+  const char* v; int64_t v_ld;
+  char* o; int64_t o_ld;
+  float* lse;
+  float* dsum;
+  uint64_t* mask;  // dropout keep bits, see mask_word()
+  float* dbias;    // optional [B * nblk][3 * H * DH] column sums of dq | dk | dv
+  const char* dout; int64_t dout_ld;
+  char* dq; int64_t dq_ld;
+  char* dk; int64_t dk_ld;
+  char* dv; int64_t dv_ld;
+  const float* rope_cos; const float* rope_sin; int rope_q, rope_k, rope_fast;
+  int B, T, H;
+  float scale;
+  uint32_t thresh; float inv_keep; uint64_t seed;
+};
+
+NSTL_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// 128-byte-row images: 16-byte chunk c of row r at c ^ att_x(r) (attention.hip)
+NSTL_DEV int att_x(int row) { return (((row >> 2) & 1) << 1) | (((row >> 1) & 1) << 2); }
+NSTL_DEV int img_off(int row, int byte) { return row * 128 + ((((byte >> 4) ^ att_x(row)) << 4) | (byte & 15)); }
+
+NSTL_DEV void dma1k(const char* src, char* dst) {
+  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
+                                   (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
+}
+// Every LDS read inside the tile loops is inline asm: with the next tile's DMA in
+// flight the compiler would put vmcnt(0) in front of its own LDS reads and drain
+// the prefetch.  The caller orders them with lgkm_fence() before the MFMAs.
+NSTL_DEV uint32_t lds_addr(const char* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p; }
+typedef int i32x4a __attribute__((ext_vector_type(4)));
+typedef int i32x2a __attribute__((ext_vector_type(2)));
+// fragment (row, elements r .. r+7) of an image
+NSTL_DEV void asm_row(bf16x8& f, const char* img, int row, int r) {
+  i32x4a v;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr(img + img_off(row, r * 2))));
+  f = __builtin_bit_cast(bf16x8, v);
+}
+// column col16 + (lane & 15) of an image whose rows are the reduction index, rows
+// r0 + 4g + 0..3 then r0 + 16 + 4g + 0..3 (acc_frag's order)
+NSTL_DEV void asm_col2(bf16x8& f, const char* img, int col16, int r0, int lane) {
+  const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+  const int byte = (col16 + 4 * pp) * 2;
+  i32x2a v0, v1;
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v0) : "v"(lds_addr(img + img_off(r0 + 4 * g + q, byte))));
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v1) : "v"(lds_addr(img + img_off(r0 + 16 + 4 * g + q, byte))));
+  const bf16x4 b0 = __builtin_bit_cast(bf16x4, v0), b1 = __builtin_bit_cast(bf16x4, v1);
+  f = (bf16x8){b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+}
+NSTL_DEV f32x4 asm_f32x4(const float* p) {
+  f32x4 v;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr((const char*)p)));
+  return v;
+}
+NSTL_DEV void lgkm_fence() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+NSTL_DEV void vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// two score registers (key tiles 2j, 2j+1) as one A / B fragment (attention.hip)
+NSTL_DEV bf16x8 acc_frag(const f32x4& a, const f32x4& b) {
+  return (bf16x8){(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
+}
+
+// dropout element index and the stored keep bits: the layout of attention.hip with
+// nt = T / 16 tiles a side -- one 64-bit word per (query tile qt, key tile kt, key % 4),
+// bit 16 * ((key % 16) / 4) + query % 16; a head's words are [qt][kt][4].
+NSTL_DEV uint64_t drop_idx(int bh, int T, int q, int k) { return ((uint64_t)bh * T + q) * T + k; }
+NSTL_DEV int64_t mask_word(int bh, int nt, int qt, int kt, int r) {
+  return (((int64_t)bh * nt + qt) * nt + kt) * 4 + r;
+}
+NSTL_DEV uint64_t shfl64(uint64_t v, int src) {
+  const uint32_t lo = __shfl((uint32_t)v, src), hi = __shfl((uint32_t)(v >> 32), src);
+  return ((uint64_t)hi << 32) | lo;
+}
+NSTL_DEV uint64_t readlane64(uint64_t v, int src) {
+  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, src);
+  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), src);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// A wave's 16 x 64 result tile (lane: rows 4g + r, column dt * 16 + (lane & 15)) to
+// global memory through the wave's 2 KB LDS scratch, as 16-byte row chunks
+NSTL_DEV void store_tile16x64(const float (&v)[4][4], char* scr, char* gbase, int64_t ld_elems, int lane) {
+  const int g = lane >> 4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) *(bf16*)(scr + (4 * g + r) * 128 + (dt * 16 + (lane & 15)) * 2) = (bf16)v[dt][r];
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int c = lane; c < 16 * 8; c += 64) {
+    const int row = c / 8, ch = c % 8;
+    *(uint4*)(gbase + (int64_t)row * ld_elems * 2 + ch * 16) = *(const uint4*)(scr + row * 128 + ch * 16);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// RoPE^T on a lane's tile elements v[dt][r] = (row0 + r, d = 16 dt + c) (attention.hip)
+NSTL_DEV float swap_pair(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+}
+NSTL_DEV void rope_tab(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, const float* cs, const float* sn) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const int i = (row0 + r) * (DH / 2) + dt * 8 + (c >> 1);
+      tc[dt][r] = cs[i];
+      ts[dt][r] = (c & 1) ? -sn[i] : sn[i];
+    }
+}
+NSTL_DEV void rope_tab_fast(float (&tc)[4][4], float (&ts)[4][4], int row0, int c) {
+  const float sgn_rev = ((c & 1) ? -1.f : 1.f) * 0.15915494309189535f;  // +-1/(2pi)
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    const float two_i = (float)(2 * (dt * 8 + (c >> 1)));
+    const float inv_freq = __expf(-9.21034049987793f * two_i / (float)DH);  // f32(ln 10000)
+    const float f = inv_freq * sgn_rev;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float a = (float)(row0 + r) * f;
+      ts[dt][r] = __builtin_amdgcn_sinf(a);
+      tc[dt][r] = __builtin_amdgcn_cosf(a);
+    }
+  }
+}
+// needs every lane of the wave active (DPP pair swaps)
+NSTL_DEV void rope_back_tile(float (&v)[4][4], int row0, int c, const float* cs, const float* sn, bool fast) {
+  float tc[4][4], ts[4][4];
+  if (fast) rope_tab_fast(tc, ts, row0, c);
+  else rope_tab(tc, ts, row0, c, cs, sn);
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const float x = v[dt][r], partner = swap_pair(x);
+      v[dt][r] = fmaf(partner, ts[dt][r], x * tc[dt][r]);
+    }
+}
+
+// Bias partials: column sums of a wave's stored (bf16) tile to red[w][64] by one
+// 16x16x16 MFMA per 16 columns (ones x tile); the last wave to arrive adds the
+// block's waves in fixed order (attention.hip)
+NSTL_DEV void wave_colsum16x64(const float (&v)[4][4], float* red, int w, int lane) {
+  const s16x4 ones = __builtin_bit_cast(s16x4, (bf16x4){(bf16)1.f, (bf16)1.f, (bf16)1.f, (bf16)1.f});
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    const bf16x4 x = {(bf16)v[dt][0], (bf16)v[dt][1], (bf16)v[dt][2], (bf16)v[dt][3]};
+    const f32x4 d = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ones, __builtin_bit_cast(s16x4, x),
+                                                              (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    if (lane < 16) red[w * 64 + dt * 16 + lane] = d[0];
+  }
+}
+NSTL_DEV bool last_to_arrive(unsigned* cnt, int nw, int lane) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's red[] writes are done
+  unsigned old = 0;
+  if (lane == 0) old = atomicAdd(cnt, 1u);
+  return __shfl(old, 0) == (unsigned)(nw - 1);
+}
+NSTL_DEV void wave_sum_out(const float* red, int nw, float* out, int lane) {
+  float cs = 0.f;
+  for (int k = 0; k < nw; ++k) cs += red[k * 64 + lane];
+  out[lane] = cs;
+}
+
+// This wave's 1 KB piece (rows 8w .. 8w + 7) of tile t of two operands into buffer
+// buf: image A at the buffer's start, image B behind it.  The source row is clamped
+// to the head's last row (a partial last tile re-reads row T - 1: finite data, never
+// past the head).
+struct TileDma {
+  const char* a; int64_t a_ldb;
+  const char* b; int64_t b_ldb;
+  int lrow, lc, T;
+  NSTL_DEV void issue(char* smem, int t, int buf, int w) const {
+    const int row = min(t * KT + lrow, T - 1);
+    dma1k(a + row * a_ldb + lc * 16, smem + buf * BUF_B + w * 1024);
+    dma1k(b + row * b_ldb + lc * 16, smem + buf * BUF_B + TILE_B + w * 1024);
+  }
+};
+NSTL_DEV TileDma tile_dma(const char* a, int64_t a_ld, const char* b, int64_t b_ld, int64_t tok0, int h, int T, int w,
+                          int lane) {
+  TileDma d;
+  d.a = a + (tok0 * a_ld + h * DH) * 2; d.a_ldb = a_ld * 2;
+  d.b = b + (tok0 * b_ld + h * DH) * 2; d.b_ldb = b_ld * 2;
+  d.lrow = w * 8 + (lane >> 3);
+  d.lc = (lane & 7) ^ att_x(d.lrow);
+  d.T = T;
+  return d;
+}
+
+// ---------------------------------------------------------------------------
+// Forward.  s[kt][r] = score(query q0 + c, key 64 t + 16 kt + 4g + r): a lane holds
+// 16 scores of ITS query per tile, the rest are in the lanes c + 16 g' (two
+// permlane swaps for the tile maximum).  The running sum stays a per-lane partial
+// (the four lanes of a query rescale by the same factor) and is reduced once at
+// the end.  LDS: 2 x (K | V) = 32 KB.
+template <bool DROP>
+__global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(LongParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int T_ = p.T, nt16 = T_ / 16, ntile = (T_ + KT - 1) / KT;
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
+  const int64_t tok0 = (int64_t)b * T_;
+  const int q0 = blockIdx.x * ROWS + w * 16;
+  const bool act = q0 < T_;
+  const TileDma dma = tile_dma(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
+  dma.issue(smem, 0, 0, w);
+  bf16x8 fq[2] = {};
+  if (act) {
+    const bf16* qrow = (const bf16*)p.q + (tok0 + q0 + c) * p.q_ld + h * DH;
+    fq[0] = *(const bf16x8*)(qrow + 8 * g);
+    fq[1] = *(const bf16x8*)(qrow + 32 + 8 * g);
+  }
+  const float c2 = p.scale * LOG2E;
+  float m = -INFINITY, lsum = 0.f;
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const uint32_t st = nstl_seed_term(p.seed);
+  for (int t = 0; t < ntile; ++t) {
+    vmcnt0();          // this wave's piece of tile t (and its stores of tile t-1)
+    __syncthreads();   // tile t has landed; every wave is done with tile t-1's buffer
+    if (t + 1 < ntile) dma.issue(smem, t + 1, (t + 1) & 1, w);
+    if (!act) continue;
+    const char* Kimg = smem + (t & 1) * BUF_B;
+    const char* Vimg = Kimg + TILE_B;
+    const int kb = t * KT;
+    f32x4 s[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; kt += 2) {
+      bf16x8 fk[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) asm_row(fk[u], Kimg, (kt + (u >> 1)) * 16 + c, 32 * (u & 1) + 8 * g);
+      lgkm_fence();
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        s[kt + u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        mma16(s[kt + u], fk[2 * u], fq[0]);
+        mma16(s[kt + u], fk[2 * u + 1], fq[1]);
+      }
+    }
+    if (kb + KT > T_) {  // the partial last tile: keys past T get probability 0
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (kb + kt * 16 + 4 * g + r >= T_) s[kt][r] = -INFINITY;
+    }
+    float mt = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) mt = fmaxf(fmaxf(mt, fmaxf(fmaxf(s[kt][0], s[kt][1]), s[kt][2])), s[kt][3]);
+    mt = max_xor16(mt);
+    mt = max_xor32(mt);
+    // every tile has >= 32 valid keys, so mn is finite; the first tile's factor is 2^-inf = 0
+    const float mn = fmaxf(m, mt);
+    const float alpha = fast_exp2((m - mn) * c2);
+    m = mn;
+    lsum *= alpha;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
+    const float nmc = -mn * c2;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = fast_exp2(fmaf(s[kt][r], c2, nmc));
+        s[kt][r] = e;
+        lsum += e;  // the row sum is taken over the undropped p
+      }
+    if constexpr (DROP) {
+      // keys (r, r+1) of this lane's query share one hash; pair index of
+      // drop_idx(bh, T, q, kb + 4g) (even): 32-bit, checked by the launcher.  Lane
+      // kt * 4 + r collects the ballot of (kt, r): the tile's 16 keep words.
+      const uint32_t pair0 = ((uint32_t)bh * T_ + (q0 + c)) * (uint32_t)(T_ >> 1) + (kb >> 1) + 2 * g;
+      uint32_t hs[4][2];
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        hs[kt][0] = nstl_pair_hash32(st, pair0 + kt * 8);
+        hs[kt][1] = nstl_pair_hash32(st, pair0 + kt * 8 + 1);
+      }
+      uint32_t mlo = 0, mhi = 0;
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const uint32_t h0 = hs[kt][0], h1 = hs[kt][1];
+        const bool k[4] = {(h0 & 0xFFFFu) >= p.thresh, (h0 >> 16) >= p.thresh, (h1 & 0xFFFFu) >= p.thresh,
+                           (h1 >> 16) >= p.thresh};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          s[kt][r] = k[r] ? s[kt][r] : 0.f;  // 1/(1-p): in the normalisation
+          const uint64_t bal = __builtin_amdgcn_ballot_w64(k[r]);
+          mlo = nstl_writelane_i32((int)(uint32_t)bal, kt * 4 + r, (int)mlo);
+          mhi = nstl_writelane_i32((int)(uint32_t)(bal >> 32), kt * 4 + r, (int)mhi);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // words of key tiles past T are not written (they would be another query tile's)
+      if (p.mask && lane < 4 * min(4, nt16 - (kb >> 4)))
+        p.mask[mask_word(bh, nt16, q0 >> 4, kb >> 4, 0) + lane] = ((uint64_t)mhi << 32) | mlo;
+    }
+    // O^T += V^T P^T over the tile's two 32-key chunks: o[dt][r] = O(query q0 + c, d = 16 dt + 4g + r)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const bf16x8 fp = acc_frag(s[2 * j], s[2 * j + 1]);
+      bf16x8 fv[4];
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) asm_col2(fv[dt], Vimg, dt * 16, 32 * j, lane);
+      lgkm_fence();
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) mma16(o[dt], fv[dt], fp);
+    }
+  }
+  if (!act) return;
+  float sum = sum_xor16(lsum);
+  sum = sum_xor32(sum);
+  const float inv = (DROP ? p.inv_keep : 1.f) * __builtin_amdgcn_rcpf(sum);
+  bf16* orow = (bf16*)p.o + (tok0 + q0 + c) * p.o_ld + h * DH + 4 * g;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    const f32x4 x = o[dt] * inv;
+    *(bf16x4*)(orow + 16 * dt) = (bf16x4){(bf16)x[0], (bf16)x[1], (bf16)x[2], (bf16)x[3]};
+  }
+  if (g == 0) p.lse[(int64_t)bh * T_ + q0 + c] = m * p.scale + logf(sum);
+}
+
+// ---------------------------------------------------------------------------
+// dQ.  Workgroup = (b, h, 128 queries); K / V tiles stream.  DM: dropout mode
+// (0 none, 1 the forward's stored keep bits, 2 re-hashed).  LDS: 2 x (K | V) =
+// 32 KB (the output staging reuses it after the sweep), bias partials, counter.
+constexpr int DQ_RED_OFF = 2 * BUF_B, DQ_ARR_OFF = DQ_RED_OFF + NW * 64 * 4;
+constexpr size_t DQ_LDS = DQ_ARR_OFF + 16;
+
+template <int DM>
+__global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(LongParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* red = (float*)(smem + DQ_RED_OFF);
+  unsigned* arrived = (unsigned*)(smem + DQ_ARR_OFF);
+  const int T_ = p.T, nt16 = T_ / 16, ntile = (T_ + KT - 1) / KT;
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
+  const int64_t tok0 = (int64_t)b * T_;
+  const int q0 = blockIdx.x * ROWS + w * 16;
+  const bool act = q0 < T_;
+  const TileDma dma = tile_dma(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
+  dma.issue(smem, 0, 0, w);
+  // stored keep bits of this wave's 16 queries against tile t: lane kt * 4 + r holds word (kt, r)
+  auto load_mask = [&](int t) -> uint64_t {
+    const int kt0 = t * (KT / 16);
+    if (lane < 4 * min(4, nt16 - kt0)) return p.mask[mask_word(bh, nt16, q0 >> 4, kt0, 0) + lane];
+    return 0;
+  };
+  bf16x8 fq[2] = {}, fo[2] = {};
+  float lq = 0.f, dqv = 0.f;  // LSE (log2 units) and D of this lane's query q0 + c
+  uint64_t mcur = 0, mnext = 0;
+  if (act) {
+    const int qr = q0 + c;
+    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DH;
+    const bf16* drow = (const bf16*)p.dout + (tok0 + qr) * p.dout_ld + h * DH;
+    const bf16* orow = (const bf16*)p.o + (tok0 + qr) * p.o_ld + h * DH;
+    bf16x8 oo[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      fq[u] = *(const bf16x8*)(qrow + 32 * u + 8 * g);
+      fo[u] = *(const bf16x8*)(drow + 32 * u + 8 * g);
+      oo[u] = *(const bf16x8*)(orow + 32 * u + 8 * g);
+    }
+    float dpart = 0.f;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dpart += (float)fo[u][e] * (float)oo[u][e];
+    dpart = sum_xor16(dpart);
+    dpart = sum_xor32(dpart);
+    if (g == 0) p.dsum[(int64_t)bh * T_ + qr] = dpart;
+    dqv = dpart;
+    lq = p.lse[(int64_t)bh * T_ + qr] * LOG2E;
+    if (DM == 1) mcur = load_mask(0);
+  }
+  if (tid == 0) *arrived = 0u;
+  const float c2 = p.scale * LOG2E;
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < ntile; ++t) {
+    vmcnt0();
+    __syncthreads();
+    if (t + 1 < ntile) {
+      if (DM == 1 && act) mnext = load_mask(t + 1);  // ahead of the DMA: its wait leaves the DMA in flight
+      dma.issue(smem, t + 1, (t + 1) & 1, w);
+    }
+    if (!act) continue;
+    const char* Kimg = smem + (t & 1) * BUF_B;
+    const char* Vimg = Kimg + TILE_B;
+    const int nc = min(2, (T_ - t * KT) / 32);  // valid 32-key chunks
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (j < nc) {
+        bf16x8 fb[8];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int row = (2 * j + u) * 16 + c;
+          asm_row(fb[4 * u + 0], Kimg, row, 8 * g);
+          asm_row(fb[4 * u + 1], Kimg, row, 32 + 8 * g);
+          asm_row(fb[4 * u + 2], Vimg, row, 8 * g);
+          asm_row(fb[4 * u + 3], Vimg, row, 32 + 8 * g);
+        }
+        lgkm_fence();
+        f32x4 dsv[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int ktl = 2 * j + u, kt = t * (KT / 16) + ktl;
+          f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+          mma16(sc, fb[4 * u + 0], fq[0]);
+          mma16(sc, fb[4 * u + 1], fq[1]);
+          mma16(dp, fb[4 * u + 2], fo[0]);
+          mma16(dp, fb[4 * u + 3], fo[1]);
+          // sc[r] / dp[r]: S^T / dP^T at (key 16 kt + 4g + r, query q0 + c)
+          bool keep[4] = {true, true, true, true};
+          if constexpr (DM == 1) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) keep[r] = (readlane64(mcur, ktl * 4 + r) >> lane) & 1;
+          } else if constexpr (DM == 2) {
+            const uint64_t idx = drop_idx(bh, T_, q0 + c, kt * 16 + 4 * g);
+            nstl_keep2(p.seed, idx, p.thresh, keep[0], keep[1]);
+            nstl_keep2(p.seed, idx + 2, p.thresh, keep[2], keep[3]);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float pv = fast_exp2(sc[r] * c2 - lq);
+            float dpd = dp[r];
+            if constexpr (DM != 0) dpd = keep[r] ? dpd * p.inv_keep : 0.f;
+            dsv[u][r] = pv * (dpd - dqv);
+          }
+        }
+        const bf16x8 fa = acc_frag(dsv[0], dsv[1]);  // dS, row = query q0 + c
+        bf16x8 fc[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) asm_col2(fc[dt], Kimg, dt * 16, 32 * j, lane);
+        lgkm_fence();
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) mma16(dq[dt], fa, fc[dt]);
+      }
+    }
+    mcur = mnext;
+  }
+  __syncthreads();  // every wave is done with the tiles: the buffers become output staging
+  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * DH : nullptr;
+  if (!act) {
+    if (bias_row) {
+      red[w * 64 + lane] = 0.f;
+      if (last_to_arrive(arrived, NW, lane)) wave_sum_out(red, NW, bias_row + h * DH, lane);
+    }
+    return;
+  }
+  float vq[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) vq[dt][r] = dq[dt][r] * p.scale;
+  if (p.rope_q) rope_back_tile(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
+  store_tile16x64(vq, smem + w * 2048, p.dq + ((tok0 + q0) * p.dq_ld + h * DH) * 2, p.dq_ld, lane);
+  if (bias_row) {
+    wave_colsum16x64(vq, red, w, lane);
+    if (last_to_arrive(arrived, NW, lane)) wave_sum_out(red, NW, bias_row + h * DH, lane);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// dK / dV.  Workgroup = (b, h, 128 keys); Q / dO tiles stream; the head's LSE and
+// D rows sit in LDS for the whole sweep.  st[r] / dpt[r]: S / dP at (query
+// 64 t + 16 qt + 4g + r, key k0 + c).  LDS: 2 x (Q | dO) = 32 KB (later the output
+// staging), lse | D (8 T bytes), bias partials, counter.
+NSTL_DEV int dkv_red_off(int T) { return 2 * BUF_B + 2 * T * 4; }
+size_t dkv_lds_bytes(int T) { return (size_t)2 * BUF_B + (size_t)2 * T * 4 + 2 * NW * 64 * 4 + 16; }
+
+template <int DM>
+__global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(LongParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int T_ = p.T, nt16 = T_ / 16, ntile = (T_ + KT - 1) / KT;
+  float* lse_s = (float*)(smem + 2 * BUF_B);
+  float* dq_s = lse_s + T_;
+  float* red = (float*)(smem + dkv_red_off(T_));  // [2][NW][64]
+  unsigned* arrived = (unsigned*)(red + 2 * NW * 64);
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
+  const int64_t tok0 = (int64_t)b * T_;
+  const int k0 = blockIdx.x * ROWS + w * 16;
+  const bool act = k0 < T_;
+  const TileDma dma = tile_dma(p.q, p.q_ld, p.dout, p.dout_ld, tok0, h, T_, w, lane);
+  dma.issue(smem, 0, 0, w);
+  for (int i = tid; i < T_; i += LNT) {
+    lse_s[i] = p.lse[(int64_t)bh * T_ + i] * LOG2E;
+    dq_s[i] = p.dsum[(int64_t)bh * T_ + i];
+  }
+  // stored keep bits of this wave's 16 keys against query tile t: lane 4 * qtl + r holds word (qtl, r)
+  auto load_mask = [&](int t) -> uint64_t {
+    const int qt = t * (KT / 16) + (lane >> 2);
+    if (lane < 16 && qt < nt16) return p.mask[mask_word(bh, nt16, qt, k0 >> 4, lane & 3)];
+    return 0;
+  };
+  bf16x8 fk[2] = {}, fv[2] = {};
+  uint64_t mcur = 0, mnext = 0;
+  if (act) {
+    const bf16* krow = (const bf16*)p.k + (tok0 + k0 + c) * p.k_ld + h * DH;
+    const bf16* vrow = (const bf16*)p.v + (tok0 + k0 + c) * p.v_ld + h * DH;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      fk[u] = *(const bf16x8*)(krow + 32 * u + 8 * g);
+      fv[u] = *(const bf16x8*)(vrow + 32 * u + 8 * g);
+    }
+    if (DM == 1) mcur = load_mask(0);
+  }
+  if (tid == 0) *arrived = 0u;
+  const float c2 = p.scale * LOG2E;
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dk[dt] = dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < ntile; ++t) {
+    vmcnt0();
+    __syncthreads();
+    if (t + 1 < ntile) {
+      if (DM == 1 && act) mnext = load_mask(t + 1);
+      dma.issue(smem, t + 1, (t + 1) & 1, w);
+    }
+    if (!act) continue;
+    const char* Qimg = smem + (t & 1) * BUF_B;
+    const char* Dimg = Qimg + TILE_B;
+    const int nc = min(2, (T_ - t * KT) / 32);  // valid 32-query chunks
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (j < nc) {
+        bf16x8 fb[8];
+        f32x4 l4[2], d4[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int row = (2 * j + u) * 16 + c;
+          asm_row(fb[4 * u + 0], Qimg, row, 8 * g);
+          asm_row(fb[4 * u + 1], Qimg, row, 32 + 8 * g);
+          asm_row(fb[4 * u + 2], Dimg, row, 8 * g);
+          asm_row(fb[4 * u + 3], Dimg, row, 32 + 8 * g);
+          const int qb = t * KT + (2 * j + u) * 16 + 4 * g;  // this lane's four queries
+          l4[u] = asm_f32x4(lse_s + qb);
+          d4[u] = asm_f32x4(dq_s + qb);
+        }
+        lgkm_fence();
+        f32x4 pdv[2], dsv[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int qtl = 2 * j + u;
+          f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
+          mma16(st, fb[4 * u + 0], fk[0]);
+          mma16(st, fb[4 * u + 1], fk[1]);
+          mma16(dpt, fb[4 * u + 2], fv[0]);
+          mma16(dpt, fb[4 * u + 3], fv[1]);
+          // keep bits of (queries 4g + r, key k0 + c): 4 consecutive bits of word (qtl, key % 4)
+          uint32_t nib = 0;
+          if (DM == 1) nib = (uint32_t)(shfl64(mcur, 4 * qtl + (lane & 3)) >> (16 * (c >> 2) + 4 * g));
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float pv = fast_exp2(st[r] * c2 - l4[u][r]);
+            float pdr = pv, dpd = dpt[r];
+            if constexpr (DM != 0) {  // P_drop's 1/(1-p) goes onto dV at the end
+              const int q = t * KT + qtl * 16 + 4 * g + r;
+              const bool keep = DM == 1 ? ((nib >> r) & 1) : nstl_keep(p.seed, drop_idx(bh, T_, q, k0 + c), p.thresh);
+              pdr = keep ? pv : 0.f;
+              dpd = keep ? dpd * p.inv_keep : 0.f;
+            }
+            pdv[u][r] = pdr;
+            dsv[u][r] = pv * (dpd - d4[u][r]);
+          }
+        }
+        const bf16x8 fa1 = acc_frag(pdv[0], pdv[1]);  // P_drop^T, row = key k0 + c
+        const bf16x8 fa2 = acc_frag(dsv[0], dsv[1]);  // dS^T
+        bf16x8 fc[8];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          asm_col2(fc[2 * dt], Dimg, dt * 16, 32 * j, lane);
+          asm_col2(fc[2 * dt + 1], Qimg, dt * 16, 32 * j, lane);
+        }
+        lgkm_fence();
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          mma16(dv[dt], fa1, fc[2 * dt]);
+          mma16(dk[dt], fa2, fc[2 * dt + 1]);
+        }
+      }
+    }
+    mcur = mnext;
+  }
+  __syncthreads();  // every wave is done with the tiles: the buffers become output staging
+  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * DH : nullptr;
+  if (!act) {
+    if (bias_row) {
+      red[w * 64 + lane] = 0.f;
+      red[NW * 64 + w * 64 + lane] = 0.f;
+      if (last_to_arrive(arrived, NW, lane)) {
+        wave_sum_out(red, NW, bias_row + p.H * DH + h * DH, lane);
+        wave_sum_out(red + NW * 64, NW, bias_row + 2 * p.H * DH + h * DH, lane);
+      }
+    }
+    return;
+  }
+  float vk[4][4], vv[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      vk[dt][r] = dk[dt][r] * p.scale;
+      vv[dt][r] = DM != 0 ? dv[dt][r] * p.inv_keep : dv[dt][r];
+    }
+  if (p.rope_k) rope_back_tile(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
+  char* scr = smem + w * 2048;
+  store_tile16x64(vk, scr, p.dk + ((tok0 + k0) * p.dk_ld + h * DH) * 2, p.dk_ld, lane);
+  store_tile16x64(vv, scr, p.dv + ((tok0 + k0) * p.dv_ld + h * DH) * 2, p.dv_ld, lane);
+  if (bias_row) {
+    wave_colsum16x64(vk, red, w, lane);
+    wave_colsum16x64(vv, red + NW * 64, w, lane);
+    if (last_to_arrive(arrived, NW, lane)) {
+      wave_sum_out(red, NW, bias_row + p.H * DH + h * DH, lane);
+      wave_sum_out(red + NW * 64, NW, bias_row + 2 * p.H * DH + h * DH, lane);
+    }
+  }
+}
+
+void fill(LongParams& p, const nstl_attn_args* a) {
+  p.q = (const char*)a->q; p.q_ld = a->q_ld;
+  p.k = (const char*)a->k; p.k_ld = a->k_ld;
+  p.v = (const char*)a->v; p.v_ld = a->v_ld;
+  p.o = (char*)a->o; p.o_ld = a->o_ld;
+  p.lse = a->lse;
+  p.dsum = a->dsum;
+  p.mask = a->mask_bits;
+  p.dbias = a->dbias_part;
+  p.dout = (const char*)a->dout; p.dout_ld = a->dout_ld;
+  p.dq = (char*)a->dq; p.dq_ld = a->dq_ld;
+  p.dk = (char*)a->dk; p.dk_ld = a->dk_ld;
+  p.dv = (char*)a->dv; p.dv_ld = a->dv_ld;
+  p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin;
+  p.rope_q = a->rope_q; p.rope_k = a->rope_k; p.rope_fast = 0;
+  p.B = a->B; p.T = a->T; p.H = a->H;
+  p.scale = 1.0f / sqrtf((float)a->dh);
+  p.thresh = nstl_drop_thresh(a->p_drop);
+  p.inv_keep = 1.0f / (1.0f - a->p_drop);
+  p.seed = a->seed;
+}
+
+template <typename K>
+int launch(K kern, dim3 grid, size_t lds, hipStream_t st, const LongParams& p, const char* what) {
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return nstl::fail((int)e, "%s: LDS request %zu: %s", what, lds, hipGetErrorString(e));
+  hipLaunchKernelGGL(kern, grid, dim3(LNT), lds, st, p);
+  NSTL_LAUNCH_CHECK(what);
+  return 0;
+}
+
+template <int DM>
+int launch_bwd(dim3 grid, hipStream_t st, const LongParams& p) {
+  int rc = launch(attn_bwd_dq_long_kernel<DM>, grid, DQ_LDS, st, p, "nstl_attn_bwd long dq");
+  if (rc) return rc;
+  return launch(attn_bwd_dkv_long_kernel<DM>, grid, dkv_lds_bytes(p.T), st, p, "nstl_attn_bwd long dkv");
+}
+
+}  // namespace
+
+namespace nstl {
+
+bool attn_long_takes(const nstl_attn_args* a) {
+  const char* e = getenv("NSTL_ATTN_LONG");
+  if (e && e[0] == '0') return false;
+  return a->dh == DH && a->dtype == NSTL_BF16 && a->T % 32 == 0 && a->T > LONG_MIN_T && a->T <= LONG_MAX_T;
+}
+
+int attn_long_fwd(const nstl_attn_args* a, hipStream_t st) {
+  LongParams p;
+  fill(p, a);
+  // the forward forms its dropout pair indices in 32 bits
+  NSTL_CHECK_ARG(!p.thresh || nstl_pair_index32_ok((uint64_t)a->B * a->H * a->T * a->T),
+                 "nstl_attn_fwd: B*H*T*T past 2^33 dropout elements (32-bit pair index)");
+  nstl::count(NSTL_K_ATTN_FWD_LONG);
+  const dim3 grid((a->T + ROWS - 1) / ROWS, a->B * a->H);
+  if (p.thresh) return launch(attn_fwd_long_kernel<true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long");
+  return launch(attn_fwd_long_kernel<false>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long");
+}
+
+int attn_long_bwd(const nstl_attn_args* a, int rope_fast, hipStream_t st) {
+  LongParams p;
+  fill(p, a);
+  p.rope_fast = rope_fast;
+  nstl::count(NSTL_K_ATTN_BWD_LONG);
+  const dim3 grid((a->T + ROWS - 1) / ROWS, a->B * a->H);
+  if (!p.thresh) return launch_bwd<0>(grid, st, p);
+  if (p.mask) return launch_bwd<1>(grid, st, p);
+  return launch_bwd<2>(grid, st, p);
+}
+
+}  // namespace nstl

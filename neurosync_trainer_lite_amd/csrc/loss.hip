@@ -9,6 +9,8 @@
 // One workgroup per sequence b: the clip is staged in LDS, per-step norms are
 // wave reductions, the gradient is written straight into the (zero-padded)
 // dpred operand of the output-head backward GEMMs.
+#include <stdlib.h>
+
 #include "../../include/nstl.h"
 #include "common.h"
 #include "status.h"
@@ -122,6 +124,109 @@ __global__ __launch_bounds__(NT) void loss_kernel(LossParams p) {
   }
 }
 
+// Clips longer than TMAX frames: the same sums over time chunks of CH frames, each
+// staged with one frame of halo on either side (the first differences, and the
+// cosine gradient's t-1 and t terms, reach one frame across a chunk edge).  The
+// step s = t0 - 1 that straddles two chunks is evaluated in both with identical
+// values, and counted in the cosine sum by the chunk that owns frame s.
+constexpr int CH = TMAX - 2;
+constexpr int TMAX_LONG = 4096;
+
+__global__ __launch_bounds__(NT) void loss_long_kernel(LossParams p) {
+  __shared__ float P[TMAX][FMAX + 1];
+  __shared__ float Y[TMAX][FMAX + 1];
+  __shared__ float s_inp[TMAX], s_iny[TMAX], s_cos[TMAX], s_np[TMAX];
+  __shared__ float red[3][NT / 64];
+  const int b = blockIdx.x, T = p.T, F = p.F;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float n_rec = (float)p.B * T * F;
+  const float n_tmp = (float)p.B * (T - 1) * F;
+  const float n_dir = (float)p.B * (T - 1);
+  const int ldd = (int)p.dpred_ld;
+  float cos_acc = 0.f, rec_acc = 0.f, tmp_acc = 0.f;
+  for (int t0 = 0; t0 < T; t0 += CH) {
+    const int t1 = min(T, t0 + CH);                       // frames this chunk owns: [t0, t1)
+    const int lo = max(t0 - 1, 0), hi = min(t1 + 1, T);  // staged frames [lo, hi), row = t - lo
+    const int n = hi - lo;
+    for (int e = tid; e < n * F; e += NT) {
+      const int lt = e / F, f = e % F;
+      P[lt][f] = p.pred[((int64_t)b * T + lo + lt) * p.pred_ld + f];
+      Y[lt][f] = p.trg[((int64_t)b * T + lo + lt) * p.trg_ld + f];
+    }
+    __syncthreads();
+    // steps lo .. hi-2 (one wave per step), row ls = step - lo
+    for (int ls = w; ls < n - 1; ls += NT / 64) {
+      float np2 = 0.f, ny2 = 0.f;
+      for (int f = lane; f < F; f += 64) {
+        const float dp = P[ls + 1][f] - P[ls][f], dy = Y[ls + 1][f] - Y[ls][f];
+        np2 += dp * dp;
+        ny2 += dy * dy;
+      }
+      const float np = sqrtf(wave_sum(np2)), ny = sqrtf(wave_sum(ny2));
+      const float inp = 1.f / (np + 1e-8f), iny = 1.f / (ny + 1e-8f);
+      float dot = 0.f;
+      for (int f = lane; f < F; f += 64) {
+        const float dp = P[ls + 1][f] - P[ls][f], dy = Y[ls + 1][f] - Y[ls][f];
+        dot += (dp * inp) * (dy * iny);
+      }
+      const float cs = wave_sum(dot);
+      if (lane == 0) {
+        if (lo + ls >= t0) cos_acc += cs;  // the halo step belongs to the previous chunk
+        s_inp[ls] = inp;
+        s_iny[ls] = iny;
+        s_cos[ls] = cs;
+        s_np[ls] = np;
+      }
+    }
+    __syncthreads();
+    auto gcos = [&](int ls, int f) {
+      const float dp = P[ls + 1][f] - P[ls][f], dy = Y[ls + 1][f] - Y[ls][f];
+      float gv = dy * s_iny[ls] * s_inp[ls];
+      const float np = s_np[ls];
+      if (np > 0.f) gv -= s_cos[ls] * dp / (np * (np + 1e-8f));
+      return gv;
+    };
+    for (int e = tid; e < (t1 - t0) * ldd; e += NT) {
+      const int t = t0 + e / ldd, f = e % ldd, lt = t - lo;
+      float g = 0.f;
+      if (f < F) {
+        const float d = P[lt][f] - Y[lt][f], ad = fabsf(d);
+        rec_acc += ad < p.delta ? 0.5f * d * d / p.delta : ad - 0.5f * p.delta;
+        g = p.w1 * (ad < p.delta ? d / p.delta : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f))) / n_rec;
+        float gd_prev = 0.f, gd_cur = 0.f;
+        if (t >= 1) {
+          const float z = (P[lt][f] - P[lt - 1][f]) - (Y[lt][f] - Y[lt - 1][f]);
+          gd_prev = p.w2 * (z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f)) / n_tmp - p.w3 * gcos(lt - 1, f) / n_dir;
+        }
+        if (t < T - 1) {
+          const float z = (P[lt + 1][f] - P[lt][f]) - (Y[lt + 1][f] - Y[lt][f]);
+          tmp_acc += fabsf(z);
+          gd_cur = p.w2 * (z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f)) / n_tmp - p.w3 * gcos(lt, f) / n_dir;
+        }
+        g = (g + gd_prev - gd_cur) * p.gscale;
+      }
+      const int64_t o = ((int64_t)b * T + t) * p.dpred_ld + f;
+      if (p.d_f32) ((float*)p.dpred)[o] = g;
+      else ((bf16*)p.dpred)[o] = (bf16)g;
+    }
+    __syncthreads();  // the next chunk restages P / Y and the step scalars
+  }
+  rec_acc = wave_sum(rec_acc);
+  tmp_acc = wave_sum(tmp_acc);
+  cos_acc = wave_sum(cos_acc);
+  if (lane == 0) {
+    red[0][w] = rec_acc;
+    red[1][w] = tmp_acc;
+    red[2][w] = cos_acc;
+  }
+  __syncthreads();
+  if (tid < 3) {
+    float s = 0.f;
+    for (int k = 0; k < NT / 64; ++k) s += red[tid][k];
+    p.partial[b * 4 + tid] = s;
+  }
+}
+
 __global__ void loss_final(LossParams p) {
   // deterministic combine over the sequences in double: lane l sums sequences
   // l, l + 64, ... in order, then a fixed butterfly over the wave
@@ -148,8 +253,9 @@ __global__ void loss_final(LossParams p) {
 
 extern "C" int nstl_loss_fwd_bwd(const nstl_loss_args* a, void* stream) {
   NSTL_CHECK_ARG(a != nullptr, "nstl_loss: null args");
-  NSTL_CHECK_ARG(a->B > 0 && a->T >= 2 && a->T <= TMAX && a->F > 0 && a->F <= FMAX,
-                 "nstl_loss: shape B=%d T=%d F=%d unsupported (T in [2,%d], F <= %d)", a->B, a->T, a->F, TMAX, FMAX);
+  NSTL_CHECK_ARG(a->B > 0 && a->T >= 2 && a->T <= TMAX_LONG && a->F > 0 && a->F <= FMAX,
+                 "nstl_loss: shape B=%d T=%d F=%d unsupported (T in [2,%d], F <= %d)", a->B, a->T, a->F, TMAX_LONG,
+                 FMAX);
   NSTL_CHECK_ARG(a->pred && a->trg && a->dpred && a->partial && a->loss_out, "nstl_loss: null tensor");
   NSTL_CHECK_ARG(a->dpred_ld >= a->F && a->pred_ld >= a->F && a->trg_ld >= a->F, "nstl_loss: ld < F");
   NSTL_CHECK_ARG(a->delta > 0.f, "nstl_loss: delta must be > 0");
@@ -161,7 +267,10 @@ extern "C" int nstl_loss_fwd_bwd(const nstl_loss_args* a, void* stream) {
   p.dpred = (char*)a->dpred; p.d_f32 = a->dpred_dtype == NSTL_F32; p.dpred_ld = a->dpred_ld;
   p.partial = a->partial; p.out = a->loss_out;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(loss_kernel, dim3(a->B), dim3(NT), 0, st, p);
+  // NSTL_LOSS_CHUNKED=1: the chunked kernel also where the whole clip fits (tests; read per call)
+  const char* e = getenv("NSTL_LOSS_CHUNKED");
+  if (a->T > TMAX || (e && e[0] == '1')) hipLaunchKernelGGL(loss_long_kernel, dim3(a->B), dim3(NT), 0, st, p);
+  else hipLaunchKernelGGL(loss_kernel, dim3(a->B), dim3(NT), 0, st, p);
   NSTL_LAUNCH_CHECK("nstl_loss_fwd_bwd");
   hipLaunchKernelGGL(loss_final, dim3(1), dim3(64), 0, st, p);
   NSTL_LAUNCH_CHECK("nstl_loss_fwd_bwd final");
