@@ -17,8 +17,10 @@
 // has one writer and a fixed summation order.
 // Conventions (scale, LSE, dropout on the normalised probabilities, the
 // nstl_keep(seed, drop_idx) stream, RoPE^T on dq / dk, bias partial rows) are
-// those of attention.hip, so the paths are interchangeable.  The operand images,
-// fragment orders and epilogue helpers below are the bf16 forms of that file's.
+// those of attention.hip, so the paths are interchangeable: the parameter block
+// (filled by attention.hip's entry points), the operand image and its reads, the
+// keep-bit words, the fragment order and the epilogue helpers (tile store, RoPE^T,
+// bias partials) are the one definition of each in attention_dev.h.
 //
 // Tails: T % 32 == 0, so a wave's 16 rows are all in range or all out, and a
 // tile holds 64 or (the last one) 32 valid rows.  The backward kernels only
@@ -28,189 +30,23 @@
 #include <stdlib.h>
 
 #include "../../include/nstl.h"
+#include "attention_dev.h"
 #include "attention_long.h"
 #include "common.h"
 #include "status.h"
 
 namespace {
 
-constexpr int DH = 64;
 constexpr int LNT = 512, NW = LNT / 64, ROWS = 16 * NW;  // 8 waves, 128 rows per workgroup
 constexpr int KT = 64;                                    // streamed rows per tile
 constexpr int TILE_B = KT * DH * 2, BUF_B = 2 * TILE_B;   // one image 8 KB; a buffer holds two
 constexpr int LONG_MIN_T = 256, LONG_MAX_T = 4096;        // (one-shot limit, T range of nstl_attn]
-constexpr float LOG2E = 1.4426950408889634f;
 
-struct LongParams {
-  const char* q; int64_t q_ld;
-  const char* k; int64_t k_ld;
-  const char* v; int64_t v_ld;
-  char* o; int64_t o_ld;
-  float* lse;
-  float* dsum;
-  uint64_t* mask;  // dropout keep bits, see mask_word()
-  float* dbias;    // optional [B * nblk][3 * H * DH] column sums of dq | dk | dv
-  const char* dout; int64_t dout_ld;
-  char* dq; int64_t dq_ld;
-  char* dk; int64_t dk_ld;
-  char* dv; int64_t dv_ld;
-  const float* rope_cos; const float* rope_sin; int rope_q, rope_k, rope_fast;
-  int B, T, H;
-  float scale;
-  uint32_t thresh; float inv_keep; uint64_t seed;
-};
-
-NSTL_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// 128-byte-row images: 16-byte chunk c of row r at c ^ att_x(r) (attention.hip)
-NSTL_DEV int att_x(int row) { return (((row >> 2) & 1) << 1) | (((row >> 1) & 1) << 2); }
-NSTL_DEV int img_off(int row, int byte) { return row * 128 + ((((byte >> 4) ^ att_x(row)) << 4) | (byte & 15)); }
-
-NSTL_DEV void dma1k(const char* src, char* dst) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                   (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
-}
-// Every LDS read inside the tile loops is inline asm: with the next tile's DMA in
-// flight the compiler would put vmcnt(0) in front of its own LDS reads and drain
-// the prefetch.  The caller orders them with lgkm_fence() before the MFMAs.
-NSTL_DEV uint32_t lds_addr(const char* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p; }
-typedef int i32x4a __attribute__((ext_vector_type(4)));
-typedef int i32x2a __attribute__((ext_vector_type(2)));
-// fragment (row, elements r .. r+7) of an image
-NSTL_DEV void asm_row(bf16x8& f, const char* img, int row, int r) {
-  i32x4a v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr(img + img_off(row, r * 2))));
-  f = __builtin_bit_cast(bf16x8, v);
-}
-// column col16 + (lane & 15) of an image whose rows are the reduction index, rows
-// r0 + 4g + 0..3 then r0 + 16 + 4g + 0..3 (acc_frag's order)
-NSTL_DEV void asm_col2(bf16x8& f, const char* img, int col16, int r0, int lane) {
-  const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-  const int byte = (col16 + 4 * pp) * 2;
-  i32x2a v0, v1;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v0) : "v"(lds_addr(img + img_off(r0 + 4 * g + q, byte))));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v1) : "v"(lds_addr(img + img_off(r0 + 16 + 4 * g + q, byte))));
-  const bf16x4 b0 = __builtin_bit_cast(bf16x4, v0), b1 = __builtin_bit_cast(bf16x4, v1);
-  f = (bf16x8){b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-}
 NSTL_DEV f32x4 asm_f32x4(const float* p) {
   f32x4 v;
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr((const char*)p)));
   return v;
 }
-NSTL_DEV void lgkm_fence() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-NSTL_DEV void vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// two score registers (key tiles 2j, 2j+1) as one A / B fragment (attention.hip)
-NSTL_DEV bf16x8 acc_frag(const f32x4& a, const f32x4& b) {
-  return (bf16x8){(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-}
-
-// dropout element index and the stored keep bits: the layout of attention.hip with
-// nt = T / 16 tiles a side -- one 64-bit word per (query tile qt, key tile kt, key % 4),
-// bit 16 * ((key % 16) / 4) + query % 16; a head's words are [qt][kt][4].
-NSTL_DEV uint64_t drop_idx(int bh, int T, int q, int k) { return ((uint64_t)bh * T + q) * T + k; }
-NSTL_DEV int64_t mask_word(int bh, int nt, int qt, int kt, int r) {
-  return (((int64_t)bh * nt + qt) * nt + kt) * 4 + r;
-}
-NSTL_DEV uint64_t shfl64(uint64_t v, int src) {
-  const uint32_t lo = __shfl((uint32_t)v, src), hi = __shfl((uint32_t)(v >> 32), src);
-  return ((uint64_t)hi << 32) | lo;
-}
-NSTL_DEV uint64_t readlane64(uint64_t v, int src) {
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, src);
-  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), src);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// A wave's 16 x 64 result tile (lane: rows 4g + r, column dt * 16 + (lane & 15)) to
-// global memory through the wave's 2 KB LDS scratch, as 16-byte row chunks
-NSTL_DEV void store_tile16x64(const float (&v)[4][4], char* scr, char* gbase, int64_t ld_elems, int lane) {
-  const int g = lane >> 4;
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) *(bf16*)(scr + (4 * g + r) * 128 + (dt * 16 + (lane & 15)) * 2) = (bf16)v[dt][r];
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int c = lane; c < 16 * 8; c += 64) {
-    const int row = c / 8, ch = c % 8;
-    *(uint4*)(gbase + (int64_t)row * ld_elems * 2 + ch * 16) = *(const uint4*)(scr + row * 128 + ch * 16);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-// RoPE^T on a lane's tile elements v[dt][r] = (row0 + r, d = 16 dt + c) (attention.hip)
-NSTL_DEV float swap_pair(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-}
-NSTL_DEV void rope_tab(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, const float* cs, const float* sn) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      const int i = (row0 + r) * (DH / 2) + dt * 8 + (c >> 1);
-      tc[dt][r] = cs[i];
-      ts[dt][r] = (c & 1) ? -sn[i] : sn[i];
-    }
-}
-NSTL_DEV void rope_tab_fast(float (&tc)[4][4], float (&ts)[4][4], int row0, int c) {
-  const float sgn_rev = ((c & 1) ? -1.f : 1.f) * 0.15915494309189535f;  // +-1/(2pi)
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    const float two_i = (float)(2 * (dt * 8 + (c >> 1)));
-    const float inv_freq = __expf(-9.21034049987793f * two_i / (float)DH);  // f32(ln 10000)
-    const float f = inv_freq * sgn_rev;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float a = (float)(row0 + r) * f;
-      ts[dt][r] = __builtin_amdgcn_sinf(a);
-      tc[dt][r] = __builtin_amdgcn_cosf(a);
-    }
-  }
-}
-// needs every lane of the wave active (DPP pair swaps)
-NSTL_DEV void rope_back_tile(float (&v)[4][4], int row0, int c, const float* cs, const float* sn, bool fast) {
-  float tc[4][4], ts[4][4];
-  if (fast) rope_tab_fast(tc, ts, row0, c);
-  else rope_tab(tc, ts, row0, c, cs, sn);
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      const float x = v[dt][r], partner = swap_pair(x);
-      v[dt][r] = fmaf(partner, ts[dt][r], x * tc[dt][r]);
-    }
-}
-
-// Bias partials: column sums of a wave's stored (bf16) tile to red[w][64] by one
-// 16x16x16 MFMA per 16 columns (ones x tile); the last wave to arrive adds the
-// block's waves in fixed order (attention.hip)
-NSTL_DEV void wave_colsum16x64(const float (&v)[4][4], float* red, int w, int lane) {
-  const s16x4 ones = __builtin_bit_cast(s16x4, (bf16x4){(bf16)1.f, (bf16)1.f, (bf16)1.f, (bf16)1.f});
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    const bf16x4 x = {(bf16)v[dt][0], (bf16)v[dt][1], (bf16)v[dt][2], (bf16)v[dt][3]};
-    const f32x4 d = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ones, __builtin_bit_cast(s16x4, x),
-                                                              (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    if (lane < 16) red[w * 64 + dt * 16 + lane] = d[0];
-  }
-}
-NSTL_DEV bool last_to_arrive(unsigned* cnt, int nw, int lane) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's red[] writes are done
-  unsigned old = 0;
-  if (lane == 0) old = atomicAdd(cnt, 1u);
-  return __shfl(old, 0) == (unsigned)(nw - 1);
-}
-NSTL_DEV void wave_sum_out(const float* red, int nw, float* out, int lane) {
-  float cs = 0.f;
-  for (int k = 0; k < nw; ++k) cs += red[k * 64 + lane];
-  out[lane] = cs;
-}
-
 // This wave's 1 KB piece (rows 8w .. 8w + 7) of tile t of two operands into buffer
 // buf: image A at the buffer's start, image B behind it.  The source row is clamped
 // to the head's last row (a partial last tile re-reads row T - 1: finite data, never
@@ -243,7 +79,7 @@ NSTL_DEV TileDma tile_dma(const char* a, int64_t a_ld, const char* b, int64_t b_
 // (the four lanes of a query rescale by the same factor) and is reduced once at
 // the end.  LDS: 2 x (K | V) = 32 KB.
 template <bool DROP>
-__global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(LongParams p) {
+__global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int T_ = p.T, nt16 = T_ / 16, ntile = (T_ + KT - 1) / KT;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
@@ -267,7 +103,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(LongParams p) {
   for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const uint32_t st = nstl_seed_term(p.seed);
   for (int t = 0; t < ntile; ++t) {
-    vmcnt0();          // this wave's piece of tile t (and its stores of tile t-1)
+    vmcnt_wait<0>();          // this wave's piece of tile t (and its stores of tile t-1)
     __syncthreads();   // tile t has landed; every wave is done with tile t-1's buffer
     if (t + 1 < ntile) dma.issue(smem, t + 1, (t + 1) & 1, w);
     if (!act) continue;
@@ -279,7 +115,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(LongParams p) {
     for (int kt = 0; kt < 4; kt += 2) {
       bf16x8 fk[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) asm_row(fk[u], Kimg, (kt + (u >> 1)) * 16 + c, 32 * (u & 1) + 8 * g);
+      for (int u = 0; u < 4; ++u) asm_row128(fk[u], Kimg, (kt + (u >> 1)) * 16 + c, 32 * (u & 1) + 8 * g);
       lgkm_fence();
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -349,10 +185,10 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(LongParams p) {
     // O^T += V^T P^T over the tile's two 32-key chunks: o[dt][r] = O(query q0 + c, d = 16 dt + 4g + r)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const bf16x8 fp = acc_frag(s[2 * j], s[2 * j + 1]);
+      const bf16x8 fp = acc_frag<bf16>(s[2 * j], s[2 * j + 1]);
       bf16x8 fv[4];
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) asm_col2(fv[dt], Vimg, dt * 16, 32 * j, lane);
+      for (int dt = 0; dt < 4; ++dt) asm_col2_128(fv[dt], Vimg, dt * 16, 32 * j, lane);
       lgkm_fence();
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) mma16(o[dt], fv[dt], fp);
@@ -379,7 +215,7 @@ constexpr int DQ_RED_OFF = 2 * BUF_B, DQ_ARR_OFF = DQ_RED_OFF + NW * 64 * 4;
 constexpr size_t DQ_LDS = DQ_ARR_OFF + 16;
 
 template <int DM>
-__global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(LongParams p) {
+__global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* red = (float*)(smem + DQ_RED_OFF);
   unsigned* arrived = (unsigned*)(smem + DQ_ARR_OFF);
@@ -431,7 +267,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(LongParams p) 
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int t = 0; t < ntile; ++t) {
-    vmcnt0();
+    vmcnt_wait<0>();
     __syncthreads();
     if (t + 1 < ntile) {
       if (DM == 1 && act) mnext = load_mask(t + 1);  // ahead of the DMA: its wait leaves the DMA in flight
@@ -448,10 +284,10 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(LongParams p) 
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const int row = (2 * j + u) * 16 + c;
-          asm_row(fb[4 * u + 0], Kimg, row, 8 * g);
-          asm_row(fb[4 * u + 1], Kimg, row, 32 + 8 * g);
-          asm_row(fb[4 * u + 2], Vimg, row, 8 * g);
-          asm_row(fb[4 * u + 3], Vimg, row, 32 + 8 * g);
+          asm_row128(fb[4 * u + 0], Kimg, row, 8 * g);
+          asm_row128(fb[4 * u + 1], Kimg, row, 32 + 8 * g);
+          asm_row128(fb[4 * u + 2], Vimg, row, 8 * g);
+          asm_row128(fb[4 * u + 3], Vimg, row, 32 + 8 * g);
         }
         lgkm_fence();
         f32x4 dsv[2];
@@ -481,10 +317,10 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(LongParams p) 
             dsv[u][r] = pv * (dpd - dqv);
           }
         }
-        const bf16x8 fa = acc_frag(dsv[0], dsv[1]);  // dS, row = query q0 + c
+        const bf16x8 fa = acc_frag<bf16>(dsv[0], dsv[1]);  // dS, row = query q0 + c
         bf16x8 fc[4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) asm_col2(fc[dt], Kimg, dt * 16, 32 * j, lane);
+        for (int dt = 0; dt < 4; ++dt) asm_col2_128(fc[dt], Kimg, dt * 16, 32 * j, lane);
         lgkm_fence();
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) mma16(dq[dt], fa, fc[dt]);
@@ -507,9 +343,9 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(LongParams p) 
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) vq[dt][r] = dq[dt][r] * p.scale;
   if (p.rope_q) rope_back_tile(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
-  store_tile16x64(vq, smem + w * 2048, p.dq + ((tok0 + q0) * p.dq_ld + h * DH) * 2, p.dq_ld, lane);
+  store_tile16x64<bf16>(vq, smem + w * 2048, p.dq + ((tok0 + q0) * p.dq_ld + h * DH) * 2, p.dq_ld, lane);
   if (bias_row) {
-    wave_colsum16x64(vq, red, w, lane);
+    wave_colsum16x64<bf16>(vq, red, w, lane);
     if (last_to_arrive(arrived, NW, lane)) wave_sum_out(red, NW, bias_row + h * DH, lane);
   }
 }
@@ -523,7 +359,7 @@ NSTL_DEV int dkv_red_off(int T) { return 2 * BUF_B + 2 * T * 4; }
 size_t dkv_lds_bytes(int T) { return (size_t)2 * BUF_B + (size_t)2 * T * 4 + 2 * NW * 64 * 4 + 16; }
 
 template <int DM>
-__global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(LongParams p) {
+__global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int T_ = p.T, nt16 = T_ / 16, ntile = (T_ + KT - 1) / KT;
   float* lse_s = (float*)(smem + 2 * BUF_B);
@@ -566,7 +402,7 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(LongParams p) {
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dk[dt] = dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int t = 0; t < ntile; ++t) {
-    vmcnt0();
+    vmcnt_wait<0>();
     __syncthreads();
     if (t + 1 < ntile) {
       if (DM == 1 && act) mnext = load_mask(t + 1);
@@ -584,10 +420,10 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(LongParams p) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const int row = (2 * j + u) * 16 + c;
-          asm_row(fb[4 * u + 0], Qimg, row, 8 * g);
-          asm_row(fb[4 * u + 1], Qimg, row, 32 + 8 * g);
-          asm_row(fb[4 * u + 2], Dimg, row, 8 * g);
-          asm_row(fb[4 * u + 3], Dimg, row, 32 + 8 * g);
+          asm_row128(fb[4 * u + 0], Qimg, row, 8 * g);
+          asm_row128(fb[4 * u + 1], Qimg, row, 32 + 8 * g);
+          asm_row128(fb[4 * u + 2], Dimg, row, 8 * g);
+          asm_row128(fb[4 * u + 3], Dimg, row, 32 + 8 * g);
           const int qb = t * KT + (2 * j + u) * 16 + 4 * g;  // this lane's four queries
           l4[u] = asm_f32x4(lse_s + qb);
           d4[u] = asm_f32x4(dq_s + qb);
@@ -619,13 +455,13 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(LongParams p) {
             dsv[u][r] = pv * (dpd - d4[u][r]);
           }
         }
-        const bf16x8 fa1 = acc_frag(pdv[0], pdv[1]);  // P_drop^T, row = key k0 + c
-        const bf16x8 fa2 = acc_frag(dsv[0], dsv[1]);  // dS^T
+        const bf16x8 fa1 = acc_frag<bf16>(pdv[0], pdv[1]);  // P_drop^T, row = key k0 + c
+        const bf16x8 fa2 = acc_frag<bf16>(dsv[0], dsv[1]);  // dS^T
         bf16x8 fc[8];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          asm_col2(fc[2 * dt], Dimg, dt * 16, 32 * j, lane);
-          asm_col2(fc[2 * dt + 1], Qimg, dt * 16, 32 * j, lane);
+          asm_col2_128(fc[2 * dt], Dimg, dt * 16, 32 * j, lane);
+          asm_col2_128(fc[2 * dt + 1], Qimg, dt * 16, 32 * j, lane);
         }
         lgkm_fence();
 #pragma unroll
@@ -660,11 +496,11 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(LongParams p) {
     }
   if (p.rope_k) rope_back_tile(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
   char* scr = smem + w * 2048;
-  store_tile16x64(vk, scr, p.dk + ((tok0 + k0) * p.dk_ld + h * DH) * 2, p.dk_ld, lane);
-  store_tile16x64(vv, scr, p.dv + ((tok0 + k0) * p.dv_ld + h * DH) * 2, p.dv_ld, lane);
+  store_tile16x64<bf16>(vk, scr, p.dk + ((tok0 + k0) * p.dk_ld + h * DH) * 2, p.dk_ld, lane);
+  store_tile16x64<bf16>(vv, scr, p.dv + ((tok0 + k0) * p.dv_ld + h * DH) * 2, p.dv_ld, lane);
   if (bias_row) {
-    wave_colsum16x64(vk, red, w, lane);
-    wave_colsum16x64(vv, red + NW * 64, w, lane);
+    wave_colsum16x64<bf16>(vk, red, w, lane);
+    wave_colsum16x64<bf16>(vv, red + NW * 64, w, lane);
     if (last_to_arrive(arrived, NW, lane)) {
       wave_sum_out(red, NW, bias_row + p.H * DH + h * DH, lane);
       wave_sum_out(red + NW * 64, NW, bias_row + 2 * p.H * DH + h * DH, lane);
@@ -672,42 +508,11 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(LongParams p) {
   }
 }
 
-void fill(LongParams& p, const nstl_attn_args* a) {
-  p.q = (const char*)a->q; p.q_ld = a->q_ld;
-  p.k = (const char*)a->k; p.k_ld = a->k_ld;
-  p.v = (const char*)a->v; p.v_ld = a->v_ld;
-  p.o = (char*)a->o; p.o_ld = a->o_ld;
-  p.lse = a->lse;
-  p.dsum = a->dsum;
-  p.mask = a->mask_bits;
-  p.dbias = a->dbias_part;
-  p.dout = (const char*)a->dout; p.dout_ld = a->dout_ld;
-  p.dq = (char*)a->dq; p.dq_ld = a->dq_ld;
-  p.dk = (char*)a->dk; p.dk_ld = a->dk_ld;
-  p.dv = (char*)a->dv; p.dv_ld = a->dv_ld;
-  p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin;
-  p.rope_q = a->rope_q; p.rope_k = a->rope_k; p.rope_fast = 0;
-  p.B = a->B; p.T = a->T; p.H = a->H;
-  p.scale = 1.0f / sqrtf((float)a->dh);
-  p.thresh = nstl_drop_thresh(a->p_drop);
-  p.inv_keep = 1.0f / (1.0f - a->p_drop);
-  p.seed = a->seed;
-}
-
-template <typename K>
-int launch(K kern, dim3 grid, size_t lds, hipStream_t st, const LongParams& p, const char* what) {
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return nstl::fail((int)e, "%s: LDS request %zu: %s", what, lds, hipGetErrorString(e));
-  hipLaunchKernelGGL(kern, grid, dim3(LNT), lds, st, p);
-  NSTL_LAUNCH_CHECK(what);
-  return 0;
-}
-
 template <int DM>
-int launch_bwd(dim3 grid, hipStream_t st, const LongParams& p) {
-  int rc = launch(attn_bwd_dq_long_kernel<DM>, grid, DQ_LDS, st, p, "nstl_attn_bwd long dq");
+int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
+  int rc = launch(attn_bwd_dq_long_kernel<DM>, grid, DQ_LDS, st, p, "nstl_attn_bwd long dq", LNT);
   if (rc) return rc;
-  return launch(attn_bwd_dkv_long_kernel<DM>, grid, dkv_lds_bytes(p.T), st, p, "nstl_attn_bwd long dkv");
+  return launch(attn_bwd_dkv_long_kernel<DM>, grid, dkv_lds_bytes(p.T), st, p, "nstl_attn_bwd long dkv", LNT);
 }
 
 }  // namespace
@@ -720,24 +525,16 @@ bool attn_long_takes(const nstl_attn_args* a) {
   return a->dh == DH && a->dtype == NSTL_BF16 && a->T % 32 == 0 && a->T > LONG_MIN_T && a->T <= LONG_MAX_T;
 }
 
-int attn_long_fwd(const nstl_attn_args* a, hipStream_t st) {
-  LongParams p;
-  fill(p, a);
-  // the forward forms its dropout pair indices in 32 bits
-  NSTL_CHECK_ARG(!p.thresh || nstl_pair_index32_ok((uint64_t)a->B * a->H * a->T * a->T),
-                 "nstl_attn_fwd: B*H*T*T past 2^33 dropout elements (32-bit pair index)");
+int attn_long_fwd(const AttnParams& p, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_FWD_LONG);
-  const dim3 grid((a->T + ROWS - 1) / ROWS, a->B * a->H);
-  if (p.thresh) return launch(attn_fwd_long_kernel<true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long");
-  return launch(attn_fwd_long_kernel<false>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long");
+  const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
+  if (p.thresh) return launch(attn_fwd_long_kernel<true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
+  return launch(attn_fwd_long_kernel<false>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
 }
 
-int attn_long_bwd(const nstl_attn_args* a, int rope_fast, hipStream_t st) {
-  LongParams p;
-  fill(p, a);
-  p.rope_fast = rope_fast;
+int attn_long_bwd(const AttnParams& p, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_BWD_LONG);
-  const dim3 grid((a->T + ROWS - 1) / ROWS, a->B * a->H);
+  const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
   if (!p.thresh) return launch_bwd<0>(grid, st, p);
   if (p.mask) return launch_bwd<1>(grid, st, p);
   return launch_bwd<2>(grid, st, p);

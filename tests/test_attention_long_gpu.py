@@ -128,6 +128,27 @@ def test_long_fwd_bwd_against_f64(T):
     check(r["dqkv"][:, 2 * D:], ref["dv"], 3e-2, "dv T=%d" % T)
 
 
+def test_long_rope_table_vs_fast(monkeypatch):
+    """NSTL_ROPE_BWD=table through the long kernels (the switch reaches them in the
+    parameter block nstl_attn_bwd fills): RoPE^T from the tables against the
+    recomputed angles, at the smallest long shape (partial last tile and block)."""
+    T, D = 288, H * DH
+    monkeypatch.setenv("NSTL_ROPE_BWD", "table")
+    tab = run(T)
+    monkeypatch.setenv("NSTL_ROPE_BWD", "fast")
+    fast = run(T)
+    for r in (tab, fast):
+        assert long_counts(r["counts"]) == (1, 1, 0, 0, 0, 0, 0), r["counts"]
+    # RoPE does not touch o and dv
+    assert torch.equal(tab["o"], fast["o"])
+    assert torch.equal(tab["dqkv"][:, 2 * D:], fast["dqkv"][:, 2 * D:])
+    ref = reference(T)
+    for i, nm in enumerate(("dq", "dk")):
+        # recomputed angles vs the tables: the same rotation to well inside bf16 rounding
+        check(fast["dqkv"][:, i * D:(i + 1) * D], tab["dqkv"][:, i * D:(i + 1) * D], 8e-3, "fast vs table RoPE^T " + nm)
+        check(tab["dqkv"][:, i * D:(i + 1) * D], ref[nm], 3e-2, "table RoPE^T %s vs f64" % nm)
+
+
 def test_long_max_window():
     """T = 4096, the longest window: 64 tiles per sweep, 32 blocks per head, and the
     dK / dV kernel's largest LDS request (68 KB, past the 64 KB default limit).  One
