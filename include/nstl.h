@@ -130,10 +130,16 @@ int nstl_fp8_quant_cols(int x_dtype, const nstl_fp8_job* jobs, int n, void* stre
  *   one-shot MFMA : dh == 64, T % 32 == 0, T <= 256 (bf16) / 128 (f32); a head's
  *                   whole K / V in LDS, a query's score row in registers;
  *   streaming MFMA: dh == 64, bf16, T % 32 == 0, 256 < T <= 4096; key / query
- *                   tiles through LDS, online softmax (NSTL_ATTN_LONG=0: off);
+ *                   tiles through LDS, online softmax (NSTL_ATTN_LONG=0: off).
+ *                   With NSTL_ATTN_RAGGED_OK in flags also every ragged length
+ *                   (T % 32 != 0, 1 <= T <= 4096; NSTL_ATTN_RAGGED=0: off);
  *   generic       : everything else with dh % 8 == 0, dh <= 512, T <= 4096 (f32
- *                   past T = 128, ragged T, other head sizes): one wave per row,
- *                   no MFMA; a correctness path, not a training path. */
+ *                   past T = 128, other head sizes, ragged T without the flag):
+ *                   one wave per row, no MFMA; a correctness path, not a
+ *                   training path. */
+#define NSTL_ATTN_RAGGED_OK 1u /* flags bit 0: mask_bits / dbias_part are sized by nstl_attn_mask_words /
+                                  nstl_attn_bias_rows of these arguments, so a ragged T may take the streaming
+                                  MFMA kernels, whose keep-bit words number B*H*ceil(T/16)^2*4, not B*H*T*T/64 */
 typedef struct nstl_attn_args {
   int dtype;
   int B, T, H, dh;
@@ -150,7 +156,8 @@ typedef struct nstl_attn_args {
   const float* rope_cos; const float* rope_sin;  /* [T][dh/2]; non-null: dq,dk rotated back */
   int rope_q, rope_k;
   float* dsum;                /* backward scratch [B*H*T] f32: rowsum(dO * O) */
-  uint64_t* mask_bits;        /* optional [B*H*T*T/64]: the dropout keep bits.  Forward
+  uint64_t* mask_bits;        /* optional [B*H*T*T/64] ([nstl_attn_mask_words()] with
+                                 NSTL_ATTN_RAGGED_OK): the dropout keep bits.  Forward
                                  writes them, backward reads them instead of re-hashing
                                  (MFMA path: head_dim 64; ignored elsewhere).  NULL:
                                  both directions hash (seed, element). */
@@ -158,12 +165,17 @@ typedef struct nstl_attn_args {
                                  per-(batch, 128-row block) column sums of dq | dk | dv as
                                  stored = the q/k/v projection bias gradients before the
                                  final row reduction (nstl_reduce_rows). MFMA path only. */
+  unsigned flags;             /* NSTL_ATTN_*; 0: the dispatch of version 1 for every shape */
 } nstl_attn_args;
 int nstl_attn_fwd(const nstl_attn_args* args, void* stream);
 int nstl_attn_bwd(const nstl_attn_args* args, void* stream);
 /* Rows of dbias_part for these arguments, or 0 when the call takes the generic
    kernels (which do not produce it). */
 int nstl_attn_bias_rows(const nstl_attn_args* args);
+/* Keep-bit words (uint64) of mask_bits this call would write or read: 16 x 16 tiles
+   of a head, 4 words each, B*H*ceil(T/16)^2*4 on the MFMA paths (= B*H*T*T/64 when
+   T % 32 == 0), 0 on the generic path (which ignores mask_bits).  Host arithmetic. */
+int64_t nstl_attn_mask_words(const nstl_attn_args* args);
 
 /* Post-LN residual block tail: s = x + dropout(dropout(y)); out = LN(s).
  * Replaces `src = src + self.dropoutN(src2); src = self.normN(src)` at
@@ -339,6 +351,8 @@ int nstl_cmvn_delta_reduce(const float* x, int ncoef, int F, float* out, int64_t
 int nstl_reduce_frame_pairs(const double* x, int F, int cols, float* out, int64_t ld_out, int col0, void* stream);
 
 const char* nstl_last_error_string(void);
+/* ABI version: raised whenever a struct of this header changes size or layout.
+   2: nstl_attn_args.flags, nstl_attn_mask_words. */
 int nstl_version(void);
 
 /* Launch counters by kernel family, process-wide (host side, counted at each

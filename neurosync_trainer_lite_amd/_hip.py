@@ -64,8 +64,11 @@ class AttnArgs(ctypes.Structure):
         ("dout", _vp), ("dout_ld", _i64), ("dq", _vp), ("dq_ld", _i64), ("dk", _vp), ("dk_ld", _i64),
         ("dv", _vp), ("dv_ld", _i64),
         ("rope_cos", _vp), ("rope_sin", _vp), ("rope_q", _i32), ("rope_k", _i32),
-        ("dsum", _vp), ("mask_bits", _vp), ("dbias_part", _vp),
+        ("dsum", _vp), ("mask_bits", _vp), ("dbias_part", _vp), ("flags", ctypes.c_uint),
     ]
+
+
+ATTN_RAGGED_OK = 1  # NSTL_ATTN_RAGGED_OK
 
 
 class LnArgs(ctypes.Structure):
@@ -112,7 +115,7 @@ REDUCE_BATCH_MAX = 16
 EXPORTS = [
     "nstl_gemm", "nstl_gemm_grouped", "nstl_gemm_colsum_rows", "nstl_gemm_relu_mask_words",
     "nstl_gemm_workspace_bytes",
-    "nstl_attn_fwd", "nstl_attn_bwd", "nstl_attn_bias_rows", "nstl_ln_fwd", "nstl_ln_bwd",
+    "nstl_attn_fwd", "nstl_attn_bwd", "nstl_attn_bias_rows", "nstl_attn_mask_words", "nstl_ln_fwd", "nstl_ln_bwd",
     "nstl_reduce_rows", "nstl_reduce_rows_strided", "nstl_reduce_rows3", "nstl_reduce_rows_batch",
     "nstl_colsum", "nstl_rope",
     "nstl_loss_fwd_bwd", "nstl_sumsq", "nstl_adam_step", "nstl_clip_coef", "nstl_cast", "nstl_copy2d", "nstl_autocorr",
@@ -157,6 +160,9 @@ def lib():
         L.nstl_attn_bwd.argtypes = [P(AttnArgs), _vp]
         L.nstl_attn_bias_rows.argtypes = [P(AttnArgs)]
         L.nstl_attn_bias_rows.restype = _i32
+        if hasattr(L, "nstl_attn_mask_words"):  # absent from a version-1 build loaded for an A/B (NSTL_LIB_PATH)
+            L.nstl_attn_mask_words.argtypes = [P(AttnArgs)]
+            L.nstl_attn_mask_words.restype = _i64
         L.nstl_ln_fwd.argtypes = [P(LnArgs), _vp]
         L.nstl_ln_bwd.argtypes = [P(LnArgs), _vp]
         L.nstl_reduce_rows.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp]
@@ -443,8 +449,11 @@ def transpose_bf16(jobs, stream=None):
               "nstl_transpose_bf16")
 
 
-def attn_args(dtype, B, T, H, q, q_ld, k, k_ld, v, v_ld, o, o_ld, lse, p_drop, seed, dh=64):
+def attn_args(dtype, B, T, H, q, q_ld, k, k_ld, v, v_ld, o, o_ld, lse, p_drop, seed, dh=64, flags=0):
+    """`flags`: ATTN_RAGGED_OK lets a ragged T (T % 32 != 0) take the streaming MFMA
+    kernels; mask_bits / dbias_part are then sized by attn_mask_words / attn_bias_rows."""
     a = AttnArgs()
+    a.flags = flags
     a.dtype = dtype
     a.B, a.T, a.H, a.dh = B, T, H, dh
     a.q, a.q_ld, a.k, a.k_ld, a.v, a.v_ld = q, q_ld, k, k_ld, v, v_ld
@@ -456,8 +465,8 @@ def attn_args(dtype, B, T, H, q, q_ld, k, k_ld, v, v_ld, o, o_ld, lse, p_drop, s
 def attn_set(a, **ops):
     """Point the AttnArgs `a` (attn_args) at tensors, each checked against the
     extent the call addresses: q, k, v, o, dout, dq, dk, dv (row stride from the
-    tensor, B*T rows of H*dh), lse / dsum ([B*H*T] f32), mask_bits ([B*H*T*T/64]
-    words), rope_cos / rope_sin ([T][dh/2] f32), dbias_part ([rows][3*H*dh] f32,
+    tensor, B*T rows of H*dh), lse / dsum ([B*H*T] f32), mask_bits (attn_mask_words
+    words; [B*H*T*T/64] where the call takes the generic kernels), rope_cos / rope_sin ([T][dh/2] f32), dbias_part ([rows][3*H*dh] f32,
     rows = attn_bias_rows)."""
     rows, cols = a.B * a.T, a.H * a.dh
     for name, t in ops.items():
@@ -471,7 +480,8 @@ def attn_set(a, **ops):
         elif name in ("lse", "dsum"):
             _check_side(t, a.B * a.H * a.T, "nstl_attn %s [B*H*T]" % name)
         elif name == "mask_bits":
-            _check_side(t, a.B * a.H * a.T * a.T // 64, "nstl_attn mask_bits [B*H*T*T/64]")
+            _check_side(t, attn_mask_words(a) or a.B * a.H * a.T * a.T // 64,
+                        "nstl_attn mask_bits [B*H*ceil(T/16)^2*4]")
         elif name in ("rope_cos", "rope_sin"):
             _check_side(t, a.T * (a.dh // 2), "nstl_attn %s [T][dh/2]" % name)
         elif name == "dbias_part":
@@ -484,6 +494,13 @@ def attn_set(a, **ops):
 
 def attn_bias_rows(a):
     return lib().nstl_attn_bias_rows(ctypes.byref(a))
+
+
+def attn_mask_words(a):
+    """Keep-bit words of mask_bits this call would use (0: the generic kernels, or a
+    version-1 build, which has no ragged path and no size query: T*T/64 per head)."""
+    fn = getattr(lib(), "nstl_attn_mask_words", None)
+    return fn(ctypes.byref(a)) if fn is not None else 0
 
 
 def attn_fwd(a, stream=None):

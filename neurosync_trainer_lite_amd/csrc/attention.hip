@@ -1438,3 +1438,9 @@ extern "C" int nstl_attn_bias_rows(const nstl_attn_args* a) {
   if (a == nullptr || !(use_fast(a) || nstl::attn_long_takes(a))) return 0;
   return a->B * ((a->T + BWD_ROWS - 1) / BWD_ROWS);
 }
+
+extern "C" int64_t nstl_attn_mask_words(const nstl_attn_args* a) {
+  if (a == nullptr || !(use_fast(a) || nstl::attn_long_takes(a))) return 0;
+  const int64_t nt = (a->T + 15) / 16;
+  return (int64_t)a->B * a->H * nt * nt * 4;
+}

@@ -124,8 +124,9 @@ NSTL_DEV uint64_t drop_idx(int bh, int T, int q, int k) { return ((uint64_t)bh *
 // Stored keep bits (MFMA paths): one 64-bit word per (query tile qt, key tile kt,
 // key % 4) of a head, bit 16 * ((key % 16) / 4) + query % 16 -- the ballot of
 // one score register r over a wave in the forward / dQ layout (lane 16g + c:
-// query c, key 4g + r).  A head's words are [qt][kt][4] with nt = T / 16 tiles a
-// side (T*T/64 of them).
+// query c, key 4g + r).  A head's words are [qt][kt][4] with nt = ceil(T / 16)
+// tiles a side (T*T/64 of them for T % 16 == 0; the streaming kernels' ragged T:
+// bits of queries / keys past T are 0).
 NSTL_DEV int64_t mask_word(int bh, int nt, int qt, int kt, int r) {
   return (((int64_t)bh * nt + qt) * nt + kt) * 4 + r;
 }
@@ -177,6 +178,25 @@ NSTL_DEV void store_tile16x64(const float (&v)[4][4], char* scr, char* gbase, in
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
+// The same with a row limit (a wave whose 16 rows straddle the end of a ragged
+// head): rows >= nrows are staged but not stored.
+template <typename T>
+NSTL_DEV void store_tile16x64(const float (&v)[4][4], char* scr, char* gbase, int64_t ld_elems, int lane, int nrows) {
+  constexpr int ESZ = (int)sizeof(T), RB = DH * ESZ, CPR = RB / 16;
+  const int g = lane >> 4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) *(T*)(scr + (4 * g + r) * RB + (dt * 16 + (lane & 15)) * ESZ) = from_f32<T>(v[dt][r]);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int c = lane; c < 16 * CPR; c += 64) {
+    const int row = c / CPR, ch = c % CPR;
+    if (row < nrows)
+      *(uint4*)(gbase + (int64_t)row * ld_elems * ESZ + ch * 16) = *(const uint4*)(scr + row * RB + ch * 16);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
 
 // RoPE^T: rotate (row t, col d) accumulator elements back by -theta
 // partner element of a RoPE pair: lane c <-> c ^ 1 (DPP quad_perm [1,0,3,2], no LDS)
@@ -198,6 +218,20 @@ NSTL_DEV void rope_tab(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, co
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       const int i = (row0 + r) * RS + dt * 8 + (c >> 1);
+      tc[dt][r] = cs[i];
+      ts[dt][r] = (c & 1) ? -sn[i] : sn[i];
+    }
+}
+// rope_tab with the table row clamped to row_last (a ragged head's last wave: its
+// rows past the head hold zeros, but the tables end at row T - 1)
+template <int RS>
+NSTL_DEV void rope_tab(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, const float* cs, const float* sn,
+                       int row_last) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const int i = min(row0 + r, row_last) * RS + dt * 8 + (c >> 1);
       tc[dt][r] = cs[i];
       ts[dt][r] = (c & 1) ? -sn[i] : sn[i];
     }
@@ -241,6 +275,14 @@ NSTL_DEV void rope_back_tile(float (&v)[4][4], int row0, int c, const float* cs,
   float tc[4][4], ts[4][4];
   if (fast) rope_tab_fast(tc, ts, row0, c);
   else rope_tab<DH / 2>(tc, ts, row0, c, cs, sn);
+  rope_apply(v, tc, ts);
+}
+
+NSTL_DEV void rope_back_tile(float (&v)[4][4], int row0, int c, const float* cs, const float* sn, bool fast,
+                             int row_last) {
+  float tc[4][4], ts[4][4];
+  if (fast) rope_tab_fast(tc, ts, row0, c);
+  else rope_tab<DH / 2>(tc, ts, row0, c, cs, sn, row_last);
   rope_apply(v, tc, ts);
 }
 

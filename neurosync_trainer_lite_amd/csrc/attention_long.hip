@@ -1,6 +1,8 @@
 // Streaming MFMA attention for long windows (bf16, head_dim 64, T % 32 == 0,
 // 256 < T <= 4096): the shapes past the one-shot kernels of attention.hip, whose
-// score rows live in registers and whose K / V of a whole head live in LDS.
+// score rows live in registers and whose K / V of a whole head live in LDS; and,
+// for a caller that sets NSTL_ATTN_RAGGED_OK, for every ragged window (T % 32 != 0,
+// 1 <= T <= 4096), which the one-shot kernels do not take at any length.
 //
 // Here nothing of size T x T or T per lane is held.  Every kernel owns a block of
 // 128 rows of one (batch, head) -- 8 waves, 16 rows each, the wave's own rows
@@ -27,6 +29,15 @@
 // touch a tile's valid 32-row chunks.  The forward computes the whole tile: its
 // DMA clamps the row index to T - 1 (nothing is read past the head's T rows) and
 // the out-of-range scores are set to -inf, i.e. probability exactly 0.
+//
+// Ragged T is the template parameter RAG of the three kernels (the T % 32 == 0
+// instantiations are unchanged by it).  A wave whose 16 rows straddle T loads its
+// rows past the head from row T - 1 (finite, inside the head), makes their
+// contribution exactly zero (dQ: lse = +inf, D = 0; dK / dV: P selected to 0) and
+// stores nothing for them; a tile's 32-row chunks count while they hold one valid
+// row; the dK / dV kernel's LSE / D rows in LDS are padded to whole tiles with
+// +inf / 0; keep bits of rows and keys past T are stored as 0; the keep-bit words
+// have ceil(T / 16) tiles a side.
 #include <stdlib.h>
 
 #include "../../include/nstl.h"
@@ -78,10 +89,10 @@ NSTL_DEV TileDma tile_dma(const char* a, int64_t a_ld, const char* b, int64_t b_
 // permlane swaps for the tile maximum).  The running sum stays a per-lane partial
 // (the four lanes of a query rescale by the same factor) and is reduced once at
 // the end.  LDS: 2 x (K | V) = 32 KB.
-template <bool DROP>
+template <bool DROP, bool RAG = false>
 __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int T_ = p.T, nt16 = T_ / 16, ntile = (T_ + KT - 1) / KT;
+  const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
@@ -90,9 +101,13 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
   const bool act = q0 < T_;
   const TileDma dma = tile_dma(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
   dma.issue(smem, 0, 0, w);
+  // RAG: a wave that straddles T reads its rows past the head from row T - 1 and
+  // stores nothing for them
+  const int qr = RAG ? min(q0 + c, T_ - 1) : q0 + c;
+  const bool qok = !RAG || q0 + c < T_;
   bf16x8 fq[2] = {};
   if (act) {
-    const bf16* qrow = (const bf16*)p.q + (tok0 + q0 + c) * p.q_ld + h * DH;
+    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DH;
     fq[0] = *(const bf16x8*)(qrow + 8 * g);
     fq[1] = *(const bf16x8*)(qrow + 32 + 8 * g);
   }
@@ -136,7 +151,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
     for (int kt = 0; kt < 4; ++kt) mt = fmaxf(fmaxf(mt, fmaxf(fmaxf(s[kt][0], s[kt][1]), s[kt][2])), s[kt][3]);
     mt = max_xor16(mt);
     mt = max_xor32(mt);
-    // every tile has >= 32 valid keys, so mn is finite; the first tile's factor is 2^-inf = 0
+    // every tile has a valid key (>= 32 of them unless RAG), so mn is finite; the first tile's factor is 2^-inf = 0
     const float mn = fmaxf(m, mt);
     const float alpha = fast_exp2((m - mn) * c2);
     m = mn;
@@ -156,12 +171,27 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
       // keys (r, r+1) of this lane's query share one hash; pair index of
       // drop_idx(bh, T, q, kb + 4g) (even): 32-bit, checked by the launcher.  Lane
       // kt * 4 + r collects the ballot of (kt, r): the tile's 16 keep words.
-      const uint32_t pair0 = ((uint32_t)bh * T_ + (q0 + c)) * (uint32_t)(T_ >> 1) + (kb >> 1) + 2 * g;
+      uint32_t pair0;
+      if (RAG && (T_ & 1)) pair0 = (uint32_t)(drop_idx(bh, T_, qr, kb + 4 * g) >> 1);
+      else pair0 = ((uint32_t)bh * T_ + qr) * (uint32_t)(T_ >> 1) + (kb >> 1) + 2 * g;
       uint32_t hs[4][2];
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
         hs[kt][0] = nstl_pair_hash32(st, pair0 + kt * 8);
         hs[kt][1] = nstl_pair_hash32(st, pair0 + kt * 8 + 1);
+      }
+      if constexpr (RAG) {
+        // odd T: a query's row of element indices starts odd for every other query,
+        // and its four keys are then the high half of pair0, pair0 + 1 and the low
+        // half of pair0 + 2: the per-element definition nstl_keep(seed, drop_idx)
+        if ((T_ & 1) && ((bh + qr) & 1)) {
+#pragma unroll
+          for (int kt = 0; kt < 4; ++kt) {
+            const uint32_t h2 = nstl_pair_hash32(st, pair0 + kt * 8 + 2);
+            hs[kt][0] = (hs[kt][0] >> 16) | (hs[kt][1] << 16);
+            hs[kt][1] = (hs[kt][1] >> 16) | (h2 << 16);
+          }
+        }
       }
       uint32_t mlo = 0, mhi = 0;
 #pragma unroll
@@ -177,6 +207,17 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
           mhi = nstl_writelane_i32((int)(uint32_t)(bal >> 32), kt * 4 + r, (int)mhi);
         }
         __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (RAG) {
+        // bits of queries / keys past T are stored as 0 (their p is 0 or unstored, so
+        // only the words need it): lane L holds word (kt, r) = (L >> 2, L & 3), whose
+        // bit 16 g + c is (key 16 kt + 4 g + r, query q0 + c)
+        const int ng = min(4, max(0, (T_ - kb - 16 * (lane >> 2) - (lane & 3) + 3) >> 2));  // valid g
+        const int nq = min(16, T_ - q0);
+        uint64_t vm = ng >= 4 ? ~0ull : (1ull << (16 * ng)) - 1;
+        vm &= ((1ull << nq) - 1) * 0x0001000100010001ull;
+        mlo &= (uint32_t)vm;
+        mhi &= (uint32_t)(vm >> 32);
       }
       // words of key tiles past T are not written (they would be another query tile's)
       if (p.mask && lane < 4 * min(4, nt16 - (kb >> 4)))
@@ -198,6 +239,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
   float sum = sum_xor16(lsum);
   sum = sum_xor32(sum);
   const float inv = (DROP ? p.inv_keep : 1.f) * __builtin_amdgcn_rcpf(sum);
+  if (!qok) return;
   bf16* orow = (bf16*)p.o + (tok0 + q0 + c) * p.o_ld + h * DH + 4 * g;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
@@ -214,12 +256,12 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
 constexpr int DQ_RED_OFF = 2 * BUF_B, DQ_ARR_OFF = DQ_RED_OFF + NW * 64 * 4;
 constexpr size_t DQ_LDS = DQ_ARR_OFF + 16;
 
-template <int DM>
+template <int DM, bool RAG = false>
 __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* red = (float*)(smem + DQ_RED_OFF);
   unsigned* arrived = (unsigned*)(smem + DQ_ARR_OFF);
-  const int T_ = p.T, nt16 = T_ / 16, ntile = (T_ + KT - 1) / KT;
+  const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
@@ -237,8 +279,11 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
   bf16x8 fq[2] = {}, fo[2] = {};
   float lq = 0.f, dqv = 0.f;  // LSE (log2 units) and D of this lane's query q0 + c
   uint64_t mcur = 0, mnext = 0;
+  // RAG: queries past T of a straddling wave read row T - 1, carry lq = +inf (P = 0)
+  // and D = 0, so their dQ rows are exactly 0; they store nothing
+  const int qr = RAG ? min(q0 + c, T_ - 1) : q0 + c;
+  const bool qok = !RAG || q0 + c < T_;
   if (act) {
-    const int qr = q0 + c;
     const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DH;
     const bf16* drow = (const bf16*)p.dout + (tok0 + qr) * p.dout_ld + h * DH;
     const bf16* orow = (const bf16*)p.o + (tok0 + qr) * p.o_ld + h * DH;
@@ -256,9 +301,9 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
       for (int e = 0; e < 8; ++e) dpart += (float)fo[u][e] * (float)oo[u][e];
     dpart = sum_xor16(dpart);
     dpart = sum_xor32(dpart);
-    if (g == 0) p.dsum[(int64_t)bh * T_ + qr] = dpart;
-    dqv = dpart;
-    lq = p.lse[(int64_t)bh * T_ + qr] * LOG2E;
+    if (g == 0 && qok) p.dsum[(int64_t)bh * T_ + qr] = dpart;
+    dqv = qok ? dpart : 0.f;
+    lq = qok ? p.lse[(int64_t)bh * T_ + qr] * LOG2E : INFINITY;
     if (DM == 1) mcur = load_mask(0);
   }
   if (tid == 0) *arrived = 0u;
@@ -276,7 +321,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
     if (!act) continue;
     const char* Kimg = smem + (t & 1) * BUF_B;
     const char* Vimg = Kimg + TILE_B;
-    const int nc = min(2, (T_ - t * KT) / 32);  // valid 32-key chunks
+    const int nc = min(2, (T_ - t * KT + (RAG ? 31 : 0)) / 32);  // 32-key chunks with a valid key
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if (j < nc) {
@@ -305,13 +350,19 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
 #pragma unroll
             for (int r = 0; r < 4; ++r) keep[r] = (readlane64(mcur, ktl * 4 + r) >> lane) & 1;
           } else if constexpr (DM == 2) {
-            const uint64_t idx = drop_idx(bh, T_, q0 + c, kt * 16 + 4 * g);
-            nstl_keep2(p.seed, idx, p.thresh, keep[0], keep[1]);
-            nstl_keep2(p.seed, idx + 2, p.thresh, keep[2], keep[3]);
+            const uint64_t idx = drop_idx(bh, T_, qr, kt * 16 + 4 * g);
+            if (RAG && (T_ & 1)) {  // idx may be odd: the per-element form
+#pragma unroll
+              for (int r = 0; r < 4; ++r) keep[r] = nstl_keep(p.seed, idx + r, p.thresh);
+            } else {
+              nstl_keep2(p.seed, idx, p.thresh, keep[0], keep[1]);
+              nstl_keep2(p.seed, idx + 2, p.thresh, keep[2], keep[3]);
+            }
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float pv = fast_exp2(sc[r] * c2 - lq);
+            float pv = fast_exp2(sc[r] * c2 - lq);
+            if constexpr (RAG) pv = kt * 16 + 4 * g + r < T_ ? pv : 0.f;  // the clamped K rows are finite
             float dpd = dp[r];
             if constexpr (DM != 0) dpd = keep[r] ? dpd * p.inv_keep : 0.f;
             dsv[u][r] = pv * (dpd - dqv);
@@ -342,8 +393,14 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
   for (int r = 0; r < 4; ++r)
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) vq[dt][r] = dq[dt][r] * p.scale;
-  if (p.rope_q) rope_back_tile(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
-  store_tile16x64<bf16>(vq, smem + w * 2048, p.dq + ((tok0 + q0) * p.dq_ld + h * DH) * 2, p.dq_ld, lane);
+  char* dq_dst = p.dq + ((tok0 + q0) * p.dq_ld + h * DH) * 2;
+  if constexpr (RAG) {
+    if (p.rope_q) rope_back_tile(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1);
+    store_tile16x64<bf16>(vq, smem + w * 2048, dq_dst, p.dq_ld, lane, T_ - q0);
+  } else {
+    if (p.rope_q) rope_back_tile(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
+    store_tile16x64<bf16>(vq, smem + w * 2048, dq_dst, p.dq_ld, lane);
+  }
   if (bias_row) {
     wave_colsum16x64<bf16>(vq, red, w, lane);
     if (last_to_arrive(arrived, NW, lane)) wave_sum_out(red, NW, bias_row + h * DH, lane);
@@ -355,16 +412,21 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
 // D rows sit in LDS for the whole sweep.  st[r] / dpt[r]: S / dP at (query
 // 64 t + 16 qt + 4g + r, key k0 + c).  LDS: 2 x (Q | dO) = 32 KB (later the output
 // staging), lse | D (8 T bytes), bias partials, counter.
-NSTL_DEV int dkv_red_off(int T) { return 2 * BUF_B + 2 * T * 4; }
-size_t dkv_lds_bytes(int T) { return (size_t)2 * BUF_B + (size_t)2 * T * 4 + 2 * NW * 64 * 4 + 16; }
+// rows of each of the LSE / D arrays: T, or (ragged T) T rounded up to whole
+// 64-query tiles -- the padding rows hold lse = +inf / D = 0, and both arrays stay
+// 16-byte aligned for ds_read_b128
+int dkv_rows(int T) { return T % 32 == 0 ? T : (T + KT - 1) / KT * KT; }
+NSTL_DEV int dkv_red_off(int rows) { return 2 * BUF_B + 2 * rows * 4; }
+size_t dkv_lds_bytes(int T) { return (size_t)2 * BUF_B + (size_t)2 * dkv_rows(T) * 4 + 2 * NW * 64 * 4 + 16; }
 
-template <int DM>
+template <int DM, bool RAG = false>
 __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int T_ = p.T, nt16 = T_ / 16, ntile = (T_ + KT - 1) / KT;
+  const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
+  const int Tp = RAG ? ntile * KT : T_;  // dkv_rows(T)
   float* lse_s = (float*)(smem + 2 * BUF_B);
-  float* dq_s = lse_s + T_;
-  float* red = (float*)(smem + dkv_red_off(T_));  // [2][NW][64]
+  float* dq_s = lse_s + Tp;
+  float* red = (float*)(smem + dkv_red_off(Tp));  // [2][NW][64]
   unsigned* arrived = (unsigned*)(red + 2 * NW * 64);
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -374,9 +436,16 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   const bool act = k0 < T_;
   const TileDma dma = tile_dma(p.q, p.q_ld, p.dout, p.dout_ld, tok0, h, T_, w, lane);
   dma.issue(smem, 0, 0, w);
-  for (int i = tid; i < T_; i += LNT) {
-    lse_s[i] = p.lse[(int64_t)bh * T_ + i] * LOG2E;
-    dq_s[i] = p.dsum[(int64_t)bh * T_ + i];
+  if constexpr (RAG) {  // queries past T: P = 2^(s - inf) = 0 and dS = 0 * (dP - 0) = 0
+    for (int i = tid; i < Tp; i += LNT) {
+      lse_s[i] = i < T_ ? p.lse[(int64_t)bh * T_ + i] * LOG2E : INFINITY;
+      dq_s[i] = i < T_ ? p.dsum[(int64_t)bh * T_ + i] : 0.f;
+    }
+  } else {
+    for (int i = tid; i < T_; i += LNT) {
+      lse_s[i] = p.lse[(int64_t)bh * T_ + i] * LOG2E;
+      dq_s[i] = p.dsum[(int64_t)bh * T_ + i];
+    }
   }
   // stored keep bits of this wave's 16 keys against query tile t: lane 4 * qtl + r holds word (qtl, r)
   auto load_mask = [&](int t) -> uint64_t {
@@ -386,9 +455,13 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   };
   bf16x8 fk[2] = {}, fv[2] = {};
   uint64_t mcur = 0, mnext = 0;
+  // RAG: keys past T of a straddling wave read row T - 1 and get P = 0 below, so
+  // their dK / dV rows are exactly 0; they store nothing
+  const int kr = RAG ? min(k0 + c, T_ - 1) : k0 + c;
+  const bool kok = !RAG || k0 + c < T_;
   if (act) {
-    const bf16* krow = (const bf16*)p.k + (tok0 + k0 + c) * p.k_ld + h * DH;
-    const bf16* vrow = (const bf16*)p.v + (tok0 + k0 + c) * p.v_ld + h * DH;
+    const bf16* krow = (const bf16*)p.k + (tok0 + kr) * p.k_ld + h * DH;
+    const bf16* vrow = (const bf16*)p.v + (tok0 + kr) * p.v_ld + h * DH;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       fk[u] = *(const bf16x8*)(krow + 32 * u + 8 * g);
@@ -411,7 +484,7 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
     if (!act) continue;
     const char* Qimg = smem + (t & 1) * BUF_B;
     const char* Dimg = Qimg + TILE_B;
-    const int nc = min(2, (T_ - t * KT) / 32);  // valid 32-query chunks
+    const int nc = min(2, (T_ - t * KT + (RAG ? 31 : 0)) / 32);  // 32-query chunks with a valid query
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if (j < nc) {
@@ -443,11 +516,12 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
           if (DM == 1) nib = (uint32_t)(shfl64(mcur, 4 * qtl + (lane & 3)) >> (16 * (c >> 2) + 4 * g));
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float pv = fast_exp2(st[r] * c2 - l4[u][r]);
+            float pv = fast_exp2(st[r] * c2 - l4[u][r]);
+            if constexpr (RAG) pv = kok ? pv : 0.f;
             float pdr = pv, dpd = dpt[r];
             if constexpr (DM != 0) {  // P_drop's 1/(1-p) goes onto dV at the end
               const int q = t * KT + qtl * 16 + 4 * g + r;
-              const bool keep = DM == 1 ? ((nib >> r) & 1) : nstl_keep(p.seed, drop_idx(bh, T_, q, k0 + c), p.thresh);
+              const bool keep = DM == 1 ? ((nib >> r) & 1) : nstl_keep(p.seed, drop_idx(bh, T_, q, kr), p.thresh);
               pdr = keep ? pv : 0.f;
               dpd = keep ? dpd * p.inv_keep : 0.f;
             }
@@ -494,10 +568,18 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
       vk[dt][r] = dk[dt][r] * p.scale;
       vv[dt][r] = DM != 0 ? dv[dt][r] * p.inv_keep : dv[dt][r];
     }
-  if (p.rope_k) rope_back_tile(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
   char* scr = smem + w * 2048;
-  store_tile16x64<bf16>(vk, scr, p.dk + ((tok0 + k0) * p.dk_ld + h * DH) * 2, p.dk_ld, lane);
-  store_tile16x64<bf16>(vv, scr, p.dv + ((tok0 + k0) * p.dv_ld + h * DH) * 2, p.dv_ld, lane);
+  char* dk_dst = p.dk + ((tok0 + k0) * p.dk_ld + h * DH) * 2;
+  char* dv_dst = p.dv + ((tok0 + k0) * p.dv_ld + h * DH) * 2;
+  if constexpr (RAG) {
+    if (p.rope_k) rope_back_tile(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1);
+    store_tile16x64<bf16>(vk, scr, dk_dst, p.dk_ld, lane, T_ - k0);
+    store_tile16x64<bf16>(vv, scr, dv_dst, p.dv_ld, lane, T_ - k0);
+  } else {
+    if (p.rope_k) rope_back_tile(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
+    store_tile16x64<bf16>(vk, scr, dk_dst, p.dk_ld, lane);
+    store_tile16x64<bf16>(vv, scr, dv_dst, p.dv_ld, lane);
+  }
   if (bias_row) {
     wave_colsum16x64<bf16>(vk, red, w, lane);
     wave_colsum16x64<bf16>(vv, red + NW * 64, w, lane);
@@ -508,11 +590,15 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   }
 }
 
+template <int DM, bool RAG>
+int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
+  int rc = launch(attn_bwd_dq_long_kernel<DM, RAG>, grid, DQ_LDS, st, p, "nstl_attn_bwd long dq", LNT);
+  if (rc) return rc;
+  return launch(attn_bwd_dkv_long_kernel<DM, RAG>, grid, dkv_lds_bytes(p.T), st, p, "nstl_attn_bwd long dkv", LNT);
+}
 template <int DM>
 int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
-  int rc = launch(attn_bwd_dq_long_kernel<DM>, grid, DQ_LDS, st, p, "nstl_attn_bwd long dq", LNT);
-  if (rc) return rc;
-  return launch(attn_bwd_dkv_long_kernel<DM>, grid, dkv_lds_bytes(p.T), st, p, "nstl_attn_bwd long dkv", LNT);
+  return p.T % 32 ? launch_bwd<DM, true>(grid, st, p) : launch_bwd<DM, false>(grid, st, p);
 }
 
 }  // namespace
@@ -522,12 +608,20 @@ namespace nstl {
 bool attn_long_takes(const nstl_attn_args* a) {
   const char* e = getenv("NSTL_ATTN_LONG");
   if (e && e[0] == '0') return false;
-  return a->dh == DH && a->dtype == NSTL_BF16 && a->T % 32 == 0 && a->T > LONG_MIN_T && a->T <= LONG_MAX_T;
+  if (a->dh != DH || a->dtype != NSTL_BF16 || a->T <= 0 || a->T > LONG_MAX_T) return false;
+  if (a->T % 32 == 0) return a->T > LONG_MIN_T;
+  // ragged T, any length: only for a caller whose side buffers are sized for it
+  e = getenv("NSTL_ATTN_RAGGED");
+  return (a->flags & NSTL_ATTN_RAGGED_OK) && !(e && e[0] == '0');
 }
 
 int attn_long_fwd(const AttnParams& p, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_FWD_LONG);
   const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
+  if (p.T % 32) {
+    if (p.thresh) return launch(attn_fwd_long_kernel<true, true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
+    return launch(attn_fwd_long_kernel<false, true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
+  }
   if (p.thresh) return launch(attn_fwd_long_kernel<true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
   return launch(attn_fwd_long_kernel<false>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
 }

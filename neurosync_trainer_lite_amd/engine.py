@@ -147,7 +147,8 @@ class _Buffers:
             self.e_rmask_ok = [False] * L
             self.d_rmask_ok = [False] * L
             # attention dropout keep bits, written by the forward, read by the backward
-            nw = max(1, B * eng.H * T * T // 64)
+            # (16 x 16 tiles of a head, 4 words each: = B*H*T*T/64 for T % 32 == 0)
+            nw = max(1, B * eng.H * ((T + 15) // 16) ** 2 * 4)
             self.e_mask = [e(nw, dtype=torch.int64) for _ in range(L)]
             self.d_mask = [e(nw, dtype=torch.int64) for _ in range(L)]
             self.d_maskc = [e(nw, dtype=torch.int64) for _ in range(L)]
@@ -942,7 +943,8 @@ class Seq2SeqEngine:
             K.reduce_rows3(part, bb.n_part, self.D, outs, bf, stream=self.st)
 
     def _attn(self, q, k, v, o, lse, seed, T, B, mask=None):
-        a = K.attn_args(K.dtype_code(self.dt), B, T, self.H, 0, 0, 0, 0, 0, 0, 0, 0, 0, self.p, seed, dh=self.dh)
+        a = K.attn_args(K.dtype_code(self.dt), B, T, self.H, 0, 0, 0, 0, 0, 0, 0, 0, 0, self.p, seed, dh=self.dh,
+                        flags=K.ATTN_RAGGED_OK)
         K.attn_set(a, q=q, k=k, v=v, o=o, lse=lse, mask_bits=mask)
         K.attn_fwd(a, stream=self.st)
 
@@ -951,7 +953,8 @@ class Seq2SeqEngine:
         view) -- the projection bias gradients, reduced from the kernel's fused
         column sums.  Returns False when the call took the generic kernels (no
         sums: the caller's colsum provides them)."""
-        a = K.attn_args(K.dtype_code(self.dt), B, T, self.H, 0, 0, 0, 0, 0, 0, 0, 0, 0, self.p, seed, dh=self.dh)
+        a = K.attn_args(K.dtype_code(self.dt), B, T, self.H, 0, 0, 0, 0, 0, 0, 0, 0, 0, self.p, seed, dh=self.dh,
+                        flags=K.ATTN_RAGGED_OK)
         cs, sn = self.rope(T, self.dh)
         a.rope_q, a.rope_k = 1, 1
         K.attn_set(a, q=q, k=k, v=v, o=o, lse=lse, dout=do, dq=dq, dk=dk, dv=dv, rope_cos=cs, rope_sin=sn,

@@ -1,6 +1,8 @@
 """Attention kernels at the 228M step's shape (B=128, T=128, H=16, dh=64, bf16,
 q|k|v as slices of one [M, 3D] buffer): fwd and bwd time with dropout 0.3 vs 0
-(the difference is the counter-hash mask cost).  python tools/bench_attn.py"""
+(the difference is the counter-hash mask cost).  python tools/bench_attn.py
+NSTL_BENCH_T sets the window (B = 128 * 128 // T); a ragged T runs with
+NSTL_ATTN_RAGGED_OK, as the engine sets it (NSTL_BENCH_RAGGED=0: without)."""
 import os
 import sys
 
@@ -13,6 +15,7 @@ from neurosync_trainer_lite_amd.engine import rotation_tables  # noqa: E402
 T = int(os.environ.get("NSTL_BENCH_T", "128"))     # 256: BASELINE C5's long clips (B halved)
 B, H, DH = 128 * 128 // T, 16, 64
 D, M = H * DH, B * T
+FLAGS = K.ATTN_RAGGED_OK if os.environ.get("NSTL_BENCH_RAGGED", "1") == "1" else 0
 dev = "cuda:0"
 bf = torch.bfloat16
 
@@ -40,11 +43,11 @@ cs, sn = rotation_tables(T, DH, dev)
 extra = {}
 mask = None
 if os.environ.get("NSTL_ATTN_MASK", "1") == "1":   # stored keep bits (0: re-hash in backward)
-    mask = torch.empty(B * H * T * T // 8, dtype=torch.uint8, device=dev)
+    mask = torch.empty(B * H * ((T + 15) // 16) ** 2 * 4, dtype=torch.int64, device=dev)
 for p in [float(x) for x in os.environ.get("NSTL_BENCH_P", "0.3,0.0").split(",")]:
     def args():
         a = K.attn_args(K.BF16, B, T, H, qkv.data_ptr(), 3 * D, qkv[:, D:].data_ptr(), 3 * D,
-                        qkv[:, 2 * D:].data_ptr(), 3 * D, o.data_ptr(), D, lse.data_ptr(), p, 77)
+                        qkv[:, 2 * D:].data_ptr(), 3 * D, o.data_ptr(), D, lse.data_ptr(), p, 77, flags=FLAGS)
         a.dout, a.dout_ld = do.data_ptr(), D
         a.dq, a.dq_ld, a.dk, a.dk_ld, a.dv, a.dv_ld = (dqkv.data_ptr(), 3 * D, dqkv[:, D:].data_ptr(), 3 * D,
                                                         dqkv[:, 2 * D:].data_ptr(), 3 * D)
