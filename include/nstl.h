@@ -401,8 +401,9 @@ int nstl_copy_engine(void* dst, const void* src, int64_t bytes, void* stream);
  * slot k at slots + k * ld), and partial[b] = the sum of squares of block b of
  * out exactly as nstl_sumsq(out, n, partial, n_partial) computes it -- the
  * reduce-scatter and the clip norm's first stage (utils/training_utils.py:73)
- * in one pass over the shard.  Starts with a system-scope acquire: the slots
- * are written by other devices' copy engines. */
+ * in one pass over the shard.  ld (a multiple of 4, >= n) is the slot stride in
+ * floats; with n_slots = 0, slots and ld are not used.  Starts with a
+ * system-scope acquire: the slots are written by other devices' copy engines. */
 int nstl_shard_sum(const float* own, const float* slots, int64_t ld, int n_slots, int64_t n, float* out,
                    float* partial, int n_partial, void* stream);
 

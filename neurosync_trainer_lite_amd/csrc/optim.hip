@@ -449,7 +449,8 @@ extern "C" int nstl_shard_sum(const float* own, const float* slots, int64_t ld, 
   NSTL_CHECK_ARG(own && out && partial && n > 0 && n_partial > 0 && n_partial <= 1024 && n_slots >= 0 &&
                      (n_slots == 0 || (slots && ld >= n)),
                  "nstl_shard_sum: bad args");
-  NSTL_CHECK_ARG((((uintptr_t)own | (uintptr_t)out | (uintptr_t)slots) % 16) == 0 && ld % 4 == 0,
+  // without slots the stride is not used (a caller may pass ld = n, any n)
+  NSTL_CHECK_ARG((((uintptr_t)own | (uintptr_t)out | (uintptr_t)slots) % 16) == 0 && (n_slots == 0 || ld % 4 == 0),
                  "nstl_shard_sum: 16-byte aligned arrays and slot stride");
   hipLaunchKernelGGL(sumsq_kernel<true>, dim3(n_partial), dim3(NT), 0, (hipStream_t)stream, out, n, partial,
                      SumSrc{own, slots, ld, n_slots, out});

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.rowwise_ref import keep_pattern
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -229,25 +231,6 @@ def test_gemm_drelu_colsum_partials(M, N):
         K.gemm(dY, W, out, M, N, Kd, a_kmajor=True, b_kmajor=False, colsum_part=part)
 
 
-def _keep_pattern_np(seed, M, N, p):
-    """Keep decision of element (i, j) under common.h's dropout hash:
-    nstl_fmix32(pair ^ seed_term), low / high 16 bits against the threshold."""
-    import numpy as np
-    seed_term = (seed & 0xFFFFFFFF) ^ (((seed >> 32) * 0x27D4EB2F) & 0xFFFFFFFF)
-    thresh = int(p * 65536.0 + 0.5)
-    pair = (np.arange(M, dtype=np.uint64)[:, None] * (N // 2) + np.arange(N // 2, dtype=np.uint64)[None, :])
-    h = (pair.astype(np.uint32) ^ np.uint32(seed_term)).astype(np.uint64)
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    h ^= h >> 16
-    keep = np.empty((M, N), dtype=bool)
-    keep[:, 0::2] = (h & 0xFFFF) >= thresh
-    keep[:, 1::2] = (h >> 16) >= thresh
-    return keep
-
-
 @pytest.mark.parametrize("Kd", [256, 1024, 2048])
 def test_gemm_relu_dropout_keep_pattern_matches_hash(Kd):
     """The ring kernel's ReLU-dropout epilogue keeps element (i, j) by the dropout
@@ -264,7 +247,7 @@ def test_gemm_relu_dropout_keep_pattern_matches_hash(Kd):
     mask = torch.zeros(words, dtype=torch.int64, device=DEV)
     K.gemm(X, W, h, M, N, Kd, relu_mask=mask, **kw)
     torch.cuda.synchronize()
-    assert torch.equal((h != 0).cpu(), torch.from_numpy(_keep_pattern_np((7 << 32) + 1234, M, N, 0.3)))
+    assert torch.equal((h != 0).cpu(), torch.from_numpy(keep_pattern((7 << 32) + 1234, M, N, 0.3)))
 
 
 @pytest.mark.parametrize("M,N", [(1024, 2048), (1000, 4096)])

@@ -71,6 +71,23 @@ def learnable_corpus(root, clips, seconds, seed, sr=88200, fps=60):
     return dirs
 
 
+def corpus_loader(cfg, root):
+    """The shuffled training DataLoader over the corpus under `root`, its clips added
+    in sorted folder order.  prepare_dataloader takes them in os.listdir order, as the
+    reference does; that order belongs to the filesystem, so the same seed drew other
+    batches on another machine."""
+    from torch.utils.data import DataLoader
+    from neurosync_trainer_lite_amd.dataset.data_processing import process_folder
+    from neurosync_trainer_lite_amd.dataset.dataset import AudioFacialDataset
+    none = os.path.join(root, os.pardir, "no_clips")
+    os.makedirs(none, exist_ok=True)
+    ds = AudioFacialDataset(dict(cfg, root_dir=none))
+    for name in sorted(os.listdir(root)):
+        audio, facial = process_folder(os.path.join(root, name), cfg["sr"], include_fast=True, include_slow=False)
+        ds.add_clip(audio, facial)
+    return DataLoader(ds, batch_size=cfg["batch_size"], shuffle=True, collate_fn=AudioFacialDataset.collate_fn)
+
+
 class OracleModel:
     """process_audio_features' model interface (eval / encoder / decoder) over the
     oracle's parameters, on the CPU in fp32."""
@@ -91,7 +108,6 @@ class OracleModel:
 
 def run(steps=300, D=256, H=4, L=2, B=16, T=128, lr=1e-4, seed=0, modes=("bf16", "fp32", "fp8"), log=print):
     from neurosync_trainer_lite_amd.config import training_config
-    from neurosync_trainer_lite_amd.dataset.dataset import prepare_dataloader
     from neurosync_trainer_lite_amd.utils.audio.extraction.extract_features import extract_audio_features
     from neurosync_trainer_lite_amd.utils.audio.processing.audio_processing import process_audio_features
     from neurosync_trainer_lite_amd.utils.csv.save_csv import save_generated_data_as_csv
@@ -110,7 +126,7 @@ def run(steps=300, D=256, H=4, L=2, B=16, T=128, lr=1e-4, seed=0, modes=("bf16",
         val_dir = learnable_corpus(val_root, 1, 20.0, seed + 77)[0]
         t0 = time.perf_counter()
         torch.manual_seed(seed)
-        _, dl = prepare_dataloader(dict(cfg, root_dir=train_root, include_fast=True, include_slow=False))
+        dl = corpus_loader(cfg, train_root)
         batches = []
         while len(batches) < steps:
             for src, trg in dl:
