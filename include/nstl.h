@@ -180,7 +180,14 @@ int64_t nstl_attn_mask_words(const nstl_attn_args* args);
 /* Post-LN residual block tail: s = x + dropout(dropout(y)); out = LN(s).
  * Replaces `src = src + self.dropoutN(src2); src = self.normN(src)` at
  * utils/model.py:175-180, :198-207, the final LayerNorms :228-229, :249-250, and
- * (rot_out) the decoder-input GlobalPositionalEncoding at :246. */
+ * (rot_out) the decoder-input GlobalPositionalEncoding at :246.
+ * Width: D is a multiple of 128, 128 <= D <= 2048, in f32 and bf16; any other D
+ * returns hipErrorInvalidValue.  The q8 / q8_scale copies exist at D = 128 / 256 /
+ * 512 / 1024 only and are refused elsewhere.  At the other widths gamma and beta
+ * must be 16-byte aligned and the rope tables 8-byte aligned.
+ * Partials: the backward runs n_part blocks and block b writes row b of every
+ * partial buffer, zeros when it finds no row.  n_part <= ceil(rows / 8) is legal at
+ * every width (ceil(rows / 4) when D % 256 != 0); a larger n_part is refused. */
 typedef struct nstl_ln_args {
   int dtype; int rows, D;
   const void* x;           /* residual (dtype), may be NULL */
@@ -196,7 +203,7 @@ typedef struct nstl_ln_args {
   const float* dout;       /* f32 [rows][D] */
   float* ds;               /* f32 [rows][D] (may alias dout) */
   void* dbranch;           /* dtype: ds * masks / (1-p)^n_masks, may be NULL */
-  float* dgamma_part; float* dbeta_part; int n_part;   /* [n_part][D]; n_part <= rows/8
+  float* dgamma_part; float* dbeta_part; int n_part;   /* [n_part][D]; n_part <= ceil(rows/8)
                                                           (rows/4 when D % 256 != 0) */
   float* dbranch_part;     /* optional [n_part][D]: column sums of dbranch (the bias
                               gradient of the Linear that produced y) */

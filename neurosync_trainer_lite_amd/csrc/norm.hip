@@ -5,9 +5,11 @@
 //             (+ optional global-PE rotation of `out`, model.py:246)
 //   backward: ds = rstd * (g*gamma - mean(g*gamma) - xhat * mean(g*gamma*xhat));
 //             dbranch = ds * masks / (1-p)^n ; per-block dgamma/dbeta partials.
-// One wave per row; each lane owns VPL = D/64 columns: contiguous (D = 128), or
-// when D % 256 == 0 four-column groups 256 apart (every wave instruction then
-// covers one contiguous span).
+// D = 128 / 256 / 512 / 768 / 1024 (and the forward at every D % 256 == 0): one
+// wave per row; each lane owns VPL = D/64 columns: contiguous (D = 128), or when
+// D % 256 == 0 four- or eight-column groups 256 / 512 apart (every wave
+// instruction then covers one contiguous span).  Every other multiple of 128 up to
+// 2048: the row-cooperative kernels (a row split over the waves of a workgroup).
 #include <algorithm>
 
 #include "../../include/nstl.h"
@@ -511,6 +513,289 @@ __global__ __launch_bounds__(NT) void ln_fwd_kernel_il(LnParams p) {
   }
 }
 
+// Row-cooperative kernels for every other width (D % 128 == 0, D <= 2048): a
+// row is split over the waves of a workgroup, thread t of them owns columns
+// 4t .. 4t+3 in the forward (8-byte bf16 / 16-byte f32 accesses) and 8t .. 8t+7 in
+// the backward (16-byte accesses); a wave instruction covers one contiguous span,
+// and where D is no multiple of a wave's span the top lanes of a row's last wave idle.
+// The row statistics go through LDS (wave sums added in wave order).  In the
+// backward RCR rows are in flight per row group and pass, so one barrier serves
+// RCR rows and a thread has 8 * RCR elements of every stream outstanding.  Every
+// wave of a block runs the same number of passes (rows past the end are skipped
+// by predicate, not by leaving), so no wave is missing at a barrier.
+constexpr int NTR = 512;
+constexpr int RCR = 4;  // backward
+constexpr int RCF = 1;  // forward: many short blocks stream faster than fewer with more rows each
+
+// Forward: one row group per block, rows blockIdx.x * RCF .. + RCF - 1.
+template <typename T>
+__global__ __launch_bounds__(NTR) void ln_fwd_kernel_rc(LnParams p) {
+  __shared__ float red[2][RCF][NTR / 64];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwv = blockDim.x >> 6;
+  const int c = 4 * threadIdx.x;
+  const bool act = c < p.D;
+  const int row0 = blockIdx.x * RCF;
+  float s[RCF][4], g[4], b[4];
+  if (act) {
+    load4<float>(p.gamma + c, g);
+    load4<float>(p.beta + c, b);
+  }
+#pragma unroll
+  for (int r = 0; r < RCF; ++r) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[r][e] = 0.f;
+    if (act && row0 + r < p.rows) load4<T>((const T*)p.y + (int64_t)(row0 + r) * p.D + c, s[r]);
+  }
+  if (p.x) {
+    float xv[RCF][4];
+#pragma unroll
+    for (int r = 0; r < RCF; ++r) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xv[r][e] = 0.f;
+      if (act && row0 + r < p.rows) load4<T>((const T*)p.x + (int64_t)(row0 + r) * p.D + c, xv[r]);
+    }
+    if (p.thresh && p.n_masks > 0) {
+#pragma unroll
+      for (int r = 0; r < RCF; ++r)
+#pragma unroll
+        for (int e = 0; e < 4; e += 2) {
+          float m0, m1;
+          branch_scale2(p, (uint64_t)((int64_t)(row0 + r) * p.D + c + e), m0, m1);
+          s[r][e] *= m0;
+          s[r][e + 1] *= m1;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RCF; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[r][e] += xv[r][e];
+  } else if (p.thresh && p.n_masks > 0) {
+#pragma unroll
+    for (int r = 0; r < RCF; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; e += 2) {
+        float m0, m1;
+        branch_scale2(p, (uint64_t)((int64_t)(row0 + r) * p.D + c + e), m0, m1);
+        s[r][e] *= m0;
+        s[r][e + 1] *= m1;
+      }
+  }
+  float mean[RCF], rstd[RCF];
+#pragma unroll
+  for (int r = 0; r < RCF; ++r) {
+    const float t = wave_sum((s[r][0] + s[r][1]) + (s[r][2] + s[r][3]));
+    if (lane == 0) red[0][r][w] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < RCF; ++r) {
+    float t = 0.f;
+    for (int k = 0; k < nwv; ++k) t += red[0][r][k];
+    mean[r] = t / p.D;
+    float sq = 0.f;
+    if (act) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = s[r][e] - mean[r];
+        sq += d * d;
+      }
+    }
+    sq = wave_sum(sq);
+    if (lane == 0) red[1][r][w] = sq;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < RCF; ++r) {
+    float t = 0.f;
+    for (int k = 0; k < nwv; ++k) t += red[1][r][k];
+    rstd[r] = rsqrtf(t / p.D + p.eps);
+    if (threadIdx.x == 0 && row0 + r < p.rows) {
+      p.mean[row0 + r] = mean[r];
+      p.rstd[row0 + r] = rstd[r];
+    }
+  }
+  if (!act) return;  // past the last barrier
+#pragma unroll
+  for (int r = 0; r < RCF; ++r) {
+    const int row = row0 + r;
+    if (row >= p.rows) break;
+    const int64_t base = (int64_t)row * p.D + c;
+    if (p.s_out) store4<T>((T*)p.s_out + base, s[r]);
+    float o[4];
+    // round to the storage type first so `rot_out` rotates exactly what `out` holds
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = to_f32(from_f32<T>((s[r][e] - mean[r]) * rstd[r] * g[e] + b[e]));
+    store4<T>((T*)p.out + base, o);
+    if (p.rot_out) {
+      const int t = row % p.rope_T, half = p.D >> 1;
+      const float2 cs = *(const float2*)(p.rope_cos + (int64_t)t * half + (c >> 1));
+      const float2 sn = *(const float2*)(p.rope_sin + (int64_t)t * half + (c >> 1));
+      float rr[4];
+      rr[0] = o[0] * cs.x - o[1] * sn.x;
+      rr[1] = o[0] * sn.x + o[1] * cs.x;
+      rr[2] = o[2] * cs.y - o[3] * sn.y;
+      rr[3] = o[2] * sn.y + o[3] * cs.y;
+      store4<T>((T*)p.rot_out + base, rr);
+    }
+  }
+}
+
+// Backward: a thread owns CB = 8 columns (one 16-byte bf16 access, two for f32), so
+// a row takes WPRB = ceil(D / 512) waves and the per-row work outside the element
+// loop (two wave sums, the LDS round, addresses) is spread over twice the elements.
+// A block is NG = max(1, 8 / WPRB) row groups; group g of block b takes rows
+// (b * NG + g) + i * gridDim.x * NG, RCR of them per pass, with the next pass's rows
+// loaded before the current ones are reduced.  A thread keeps its columns over all
+// of its rows, so the per-block partials come straight from registers, summed over
+// the row groups (in group order) through LDS when NG > 1.
+constexpr int CB = 8;
+constexpr int RC_PART_LDS = 7 * 3 * 512;  // (NG - 1) * 3 * D floats at most: D = 512, NG = 8
+
+template <typename T>
+__global__ __launch_bounds__(NTR) void ln_bwd_kernel_rc(LnParams p) {
+  __shared__ float red[2][RCR][2][NTR / 64];  // [pass parity][row][a1 | a2][wave]: one barrier per pass
+  __shared__ float pr[RC_PART_LDS];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wpr = (p.D + 64 * CB - 1) / (64 * CB), ng = (int)(blockDim.x >> 6) / wpr;
+  const int g = w / wpr, w0 = g * wpr;
+  const int c = CB * ((w - w0) * 64 + lane);
+  const bool act = c < p.D;
+  const int stride = gridDim.x * ng;
+  const int first = blockIdx.x * ng + g;
+  const float inv_d = 1.0f / p.D;
+  float gam[CB], dg[CB], db[CB], dyb[CB];
+#pragma unroll
+  for (int e = 0; e < CB; ++e) gam[e] = dg[e] = db[e] = dyb[e] = 0.f;
+  if (act) loadG<float, CB>(p.gamma + c, gam);
+  float xh[RCR][CB], gy[RCR][CB], mean[RCR], rstd[RCR];
+  // rows first + (i0 + r) * stride, r < RCR; zeros where there is no such row
+  auto load = [&](int i0, float (&x)[RCR][CB], float (&gr)[RCR][CB], float (&mu)[RCR], float (&rs)[RCR]) {
+#pragma unroll
+    for (int r = 0; r < RCR; ++r) {
+      const int row = first + (i0 + r) * stride;
+      const bool ok = row < p.rows;
+#pragma unroll
+      for (int e = 0; e < CB; ++e) x[r][e] = gr[r][e] = 0.f;
+      mu[r] = rs[r] = 0.f;
+      if (ok) {
+        mu[r] = p.mean[row];
+        rs[r] = p.rstd[row];
+      }
+      if (ok && act) {
+        const int64_t base = (int64_t)row * p.D + c;
+        loadG<T, CB>((const T*)p.s_in + base, x[r]);
+        loadG<float, CB>(p.dout + base, gr[r]);
+        if (p.dout2) {
+          float a8[CB];
+          loadG<T, CB>((const T*)p.dout2 + base, a8);
+#pragma unroll
+          for (int e = 0; e < CB; ++e) gr[r][e] += a8[e];
+        }
+      }
+    }
+  };
+  load(0, xh, gy, mean, rstd);
+  // Block-uniform trip count: group 0 has the block's lowest rows, so it decides.
+  int par = 0;
+  for (int i0 = 0; blockIdx.x * ng + i0 * stride < p.rows; i0 += RCR, par ^= 1) {
+    float xn[RCR][CB], gn[RCR][CB], mn[RCR], rn[RCR];
+    load(i0 + RCR, xn, gn, mn, rn);
+#pragma unroll
+    for (int r = 0; r < RCR; ++r) {
+      float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+      for (int e = 0; e < CB; ++e) {
+        xh[r][e] = (xh[r][e] - mean[r]) * rstd[r];
+        dg[e] += gy[r][e] * xh[r][e];
+        db[e] += gy[r][e];
+        const float gg = gy[r][e] * gam[e];
+        a1 += gg;
+        a2 += gg * xh[r][e];
+      }
+      a1 = wave_sum(a1);
+      a2 = wave_sum(a2);
+      if (lane == 0) {
+        red[par][r][0][w] = a1;
+        red[par][r][1][w] = a2;
+      }
+    }
+    // the buffer of this parity was last read two passes back, ahead of the
+    // previous pass's barrier
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RCR; ++r) {
+      const int row = first + (i0 + r) * stride;
+      float m1 = 0.f, m2 = 0.f;
+      for (int k = 0; k < wpr; ++k) {
+        m1 += red[par][r][0][w0 + k];
+        m2 += red[par][r][1][w0 + k];
+      }
+      m1 *= inv_d;
+      m2 *= inv_d;
+      if (act && row < p.rows) {
+        const int64_t base = (int64_t)row * p.D + c;
+        float d[CB];
+#pragma unroll
+        for (int e = 0; e < CB; ++e) d[e] = rstd[r] * (gy[r][e] * gam[e] - m1 - xh[r][e] * m2);
+        storeG<float, CB>(p.ds + base, d);
+        if (p.dbranch) {
+          if (p.thresh && p.n_masks > 0) {
+#pragma unroll
+            for (int e = 0; e < CB; e += 2) {
+              float s0, s1;
+              branch_scale2(p, (uint64_t)base + e, s0, s1);
+              d[e] *= s0;
+              d[e + 1] *= s1;
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < CB; ++e) d[e] = to_f32(from_f32<T>(d[e]));  // sum what is stored
+          storeG<T, CB>((T*)p.dbranch + base, d);
+#pragma unroll
+          for (int e = 0; e < CB; ++e) dyb[e] += d[e];
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RCR; ++r) {
+#pragma unroll
+      for (int e = 0; e < CB; ++e) {
+        xh[r][e] = xn[r][e];
+        gy[r][e] = gn[r][e];
+      }
+      mean[r] = mn[r];
+      rstd[r] = rn[r];
+    }
+  }
+  if (ng > 1) {  // block-uniform
+    if (g > 0 && act) {
+#pragma unroll
+      for (int e = 0; e < CB; ++e) {
+        pr[((g - 1) * 3 + 0) * p.D + c + e] = dg[e];
+        pr[((g - 1) * 3 + 1) * p.D + c + e] = db[e];
+        pr[((g - 1) * 3 + 2) * p.D + c + e] = dyb[e];
+      }
+    }
+    __syncthreads();
+    if (g == 0 && act) {
+      for (int k = 0; k < ng - 1; ++k)
+#pragma unroll
+        for (int e = 0; e < CB; ++e) {
+          dg[e] += pr[(k * 3 + 0) * p.D + c + e];
+          db[e] += pr[(k * 3 + 1) * p.D + c + e];
+          dyb[e] += pr[(k * 3 + 2) * p.D + c + e];
+        }
+    }
+  }
+  if (g != 0 || !act) return;  // past the last barrier
+  const int64_t o = (int64_t)blockIdx.x * p.D + c;
+  storeG<float, CB>(p.dgp + o, dg);
+  storeG<float, CB>(p.dbp + o, db);
+  if (p.dyp) storeG<float, CB>(p.dyp + o, dyb);
+}
+
 // NSTL_LN_G8=0: four-column lane groups (8-byte bf16 accesses) when D % 512 == 0
 bool ln_g8() {
   static const int v = [] {
@@ -518,6 +803,18 @@ bool ln_g8() {
     return e && e[0] == '0' ? 0 : 1;
   }();
   return v != 0;
+}
+
+// forward at 1024 < D <= 2048, D % 256 == 0: V = D / 64 columns per lane
+template <typename T, int V>
+void launch_fwd_il(const LnParams& p, int grid, hipStream_t st) {
+  if constexpr (V % 8 == 0) {
+    if (ln_g8()) {
+      hipLaunchKernelGGL((ln_fwd_kernel_il<T, V, 8>), dim3(grid), dim3(NT), 0, st, p);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((ln_fwd_kernel_il<T, V, 4>), dim3(grid), dim3(NT), 0, st, p);
 }
 
 template <typename T, bool BWD>
@@ -539,9 +836,31 @@ int dispatch(const LnParams& p, int grid, hipStream_t st) {
     NSTL_LN_CASE(2)
     NSTL_LN_CASE(4)
     NSTL_LN_CASE(8)
+    NSTL_LN_CASE(12)
     NSTL_LN_CASE(16)
-    default:
-      return nstl::fail((int)hipErrorInvalidValue, "nstl_ln: D=%d unsupported (128/256/512/1024)", p.D);
+    default: {
+      // row-cooperative kernels: a block per RCF rows (forward) / per partial (backward)
+      if (p.D % 128 || p.D > 2048)
+        return nstl::fail((int)hipErrorInvalidValue,
+                          "nstl_ln: D=%d unsupported (a multiple of 128, 128 <= D <= 2048)", p.D);
+      if (((uintptr_t)p.gamma | (uintptr_t)p.beta) % 16 || ((uintptr_t)p.rope_cos | (uintptr_t)p.rope_sin) % 8)
+        return nstl::fail((int)hipErrorInvalidValue,
+                          "nstl_ln: D=%d needs 16-byte aligned gamma/beta and 8-byte aligned rope tables", p.D);
+      if (!BWD && p.D % 256 == 0) {  // the forward's wave-per-row kernel still fits its registers
+        switch (p.D / 64) {
+          case 20: launch_fwd_il<T, 20>(p, grid, st); break;
+          case 24: launch_fwd_il<T, 24>(p, grid, st); break;
+          case 28: launch_fwd_il<T, 28>(p, grid, st); break;
+          default: launch_fwd_il<T, 32>(p, grid, st); break;
+        }
+        break;
+      }
+      static_assert(NTR == 512, "RC_PART_LDS is sized for at most 8 row groups");
+      const int wpr = (p.D + 255) / 256;                                   // forward: 4 columns per thread
+      const int wprb = (p.D + 64 * CB - 1) / (64 * CB), ng = NTR / 64 / wprb;  // backward: 8
+      if (BWD) hipLaunchKernelGGL((ln_bwd_kernel_rc<T>), dim3(grid), dim3(ng * wprb * 64), 0, st, p);
+      else hipLaunchKernelGGL((ln_fwd_kernel_rc<T>), dim3((p.rows + RCF - 1) / RCF), dim3(wpr * 64), 0, st, p);
+    }
   }
 #undef NSTL_LN_CASE
   NSTL_LAUNCH_CHECK(BWD ? "nstl_ln_bwd" : "nstl_ln_fwd");
@@ -551,7 +870,11 @@ int dispatch(const LnParams& p, int grid, hipStream_t st) {
 int fill(LnParams& p, const nstl_ln_args* a) {
   NSTL_CHECK_ARG(a != nullptr, "nstl_ln: null args");
   NSTL_CHECK_ARG(a->dtype == NSTL_F32 || a->dtype == NSTL_BF16, "nstl_ln: bad dtype");
-  NSTL_CHECK_ARG(a->rows > 0 && a->D > 0 && a->D % 64 == 0 && a->D <= 1024, "nstl_ln: bad shape");
+  NSTL_CHECK_ARG(a->rows > 0, "nstl_ln: bad shape (rows=%d)", a->rows);
+  NSTL_CHECK_ARG(a->D >= 128 && a->D % 128 == 0 && a->D <= 2048,
+                 "nstl_ln: D=%d unsupported (a multiple of 128, 128 <= D <= 2048)", a->D);
+  NSTL_CHECK_ARG(!a->q8 || a->D == 128 || a->D == 256 || a->D == 512 || a->D == 1024,
+                 "nstl_ln: the q8 / q8_scale copy (fp8) needs D in 128/256/512/1024 (got %d)", a->D);
   NSTL_CHECK_ARG(a->gamma && a->beta, "nstl_ln: gamma/beta missing");
   NSTL_CHECK_ARG(a->n_masks >= 0 && a->n_masks <= 2 && a->p_drop >= 0.f && a->p_drop < 1.f, "nstl_ln: dropout");
   NSTL_CHECK_ARG(a->p_drop == 0.f || nstl_pair_index32_ok((uint64_t)a->rows * a->D),

@@ -60,6 +60,14 @@ def _pad64(n):
     return (n + 63) // 64 * 64
 
 
+# the LayerNorm kernels write the e4m3 side copies (nstl_ln_args.q8) at these widths only
+FP8_WIDTHS = (128, 256, 512, 1024)
+
+
+def fp8_width_error(D):
+    return "fp8 projections need hidden_dim in %s (got %d)" % (FP8_WIDTHS, D)
+
+
 _UNBOUND = object()  # Seq2SeqEngine.ensure_bound: no p.grad seen yet
 
 class _Buffers:
@@ -275,8 +283,8 @@ class Seq2SeqEngine:
         D, H = self.D, self.H
         if D % H or (D // H) % 8 or D // H > 512:
             raise ValueError("head_dim must be a multiple of 8 up to 512 (hidden_dim=%d, num_heads=%d)" % (D, H))
-        if D % 128 or D > 1024:
-            raise ValueError("hidden_dim must be a multiple of 128 and <= 1024 (got %d)" % D)
+        if D % 128 or D > 2048:
+            raise ValueError("hidden_dim must be a multiple of 128 and <= 2048 (got %d)" % D)
         if self.out_dim > 64:
             raise ValueError("output_dim must be <= 64 (got %d)" % self.out_dim)
         if self.in_dim % 8:
@@ -664,6 +672,8 @@ class Seq2SeqEngine:
     def set_fp8(self, on, scope=None, backward=None):
         if on and self.dt != torch.bfloat16:
             raise ValueError("fp8 projections need the bf16 compute dtype (use_amp=True)")
+        if on and self.D not in FP8_WIDTHS:
+            raise ValueError(fp8_width_error(self.D))
         if scope is not None:
             if scope not in self.FP8_SCOPES:
                 raise ValueError("fp8 scope must be one of %s" % (self.FP8_SCOPES,))

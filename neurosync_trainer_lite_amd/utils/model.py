@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip as K
-from ..engine import Seq2SeqEngine, Seq2SeqFunction, rotation_tables
+from ..engine import FP8_WIDTHS, Seq2SeqEngine, Seq2SeqFunction, fp8_width_error, rotation_tables
 
 
 def _require_gpu(t, what):
@@ -354,6 +354,8 @@ class Seq2Seq(nn.Module):
         LayerNorm backward, e4m3 W2^T)."""
         if on and self.compute_dtype != torch.bfloat16:
             raise ValueError("fp8 projections need the bf16 compute dtype (use_amp=True)")
+        if on and self.encoder.embedding.out_features not in FP8_WIDTHS:
+            raise ValueError(fp8_width_error(self.encoder.embedding.out_features))
         self.fp8 = bool(on)
         if scope is not None:
             self.fp8_scope = scope

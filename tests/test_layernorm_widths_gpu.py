@@ -1,0 +1,302 @@
+"""f64 parity of the LayerNorm kernels (csrc/norm.hip) at the widths beyond the
+original four: D = 384, 896 (D % 256 != 0: row-cooperative forward and backward, 8 /
+4 row groups per backward block), 768 (the wave-per-row templates at 12 columns per
+lane), 1152 (above 1024, D % 256 != 0), 1536 (D % 256 == 0, not % 512) and 2048 (the
+maximum; D % 512 == 0) (wave-per-row forward at four- / eight-column groups,
+row-cooperative backward with 2 row groups), in f32 and bf16, with 0 / 1 / 2 dropout
+masks.  The scheme, the inputs and the launch helpers are those of
+tests/test_rowwise_parity_gpu.py::test_layernorm_parity.
+
+Bounds.  That file's bounds hold here too, with one rule on top, because the f32
+rounding error of a row mean (and of everything derived from it) grows with D: for
+every quantity of every case the test evaluates the reference's formulas once more in
+float32 on the CPU (the same torch calls, so the same summation order), takes that
+restatement's error against the float64 reference in the metric of the check, and
+uses max(the existing bound, 4 x that error).  The factor 4 covers a different but
+valid summation order.  The restatement sees reference data only: the forward's from
+the inputs, the backward's from the float64 forward reference rounded to what the
+forward stores (s in the dtype, mean and rstd in f32), never a kernel output.  Where
+the existing bound stays, the restatement is asserted to lie within it.
+
+With NSTL_PARITY_ERRORS_OUT=<file> the largest measured error of each quantity is
+written next to its bound (profiles/layernorm_widths_errors.txt is such a run)."""
+import os
+
+import pytest
+import torch
+
+from tests import rowwise_ref as R
+from tests import test_rowwise_parity_gpu as P
+
+pytestmark = pytest.mark.gpu
+
+if torch.cuda.is_available():
+    from neurosync_trainer_lite_amd import _hip as K
+    from neurosync_trainer_lite_amd.engine import rotation_tables
+
+DEV = P.DEV
+F32, BF16 = P.F32, P.BF16
+LN_P, LN_EPS, LN_SEEDS = P.LN_P, P.LN_EPS, P.LN_SEEDS
+WIDTHS = [384, 768, 896, 1152, 1536, 2048]
+MARGIN = 4.0
+
+_ERRORS = {}  # quantity -> (fraction of the bound used, bound, measured)
+
+
+def _note(what, frac, bound, measured):
+    if what not in _ERRORS or frac > _ERRORS[what][0]:
+        _ERRORS[what] = (frac, bound, measured)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _error_report():
+    yield
+    path = os.environ.get("NSTL_PARITY_ERRORS_OUT")
+    if path and _ERRORS:
+        with open(path, "w") as f:
+            f.write("# tests/test_layernorm_widths_gpu.py: largest measured error of each quantity next to its bound\n")
+            f.write("# (the bound of the case that came closest to it; existing bound or 4 x the f32 restatement's error)\n")
+            f.write("# %-38s %-36s %-30s %s\n" % ("quantity", "bound", "measured", "measured / bound"))
+            for what in sorted(_ERRORS):
+                frac, bound, measured = _ERRORS[what]
+                f.write("%-40s %-36s %-30s %.4f\n" % (what, bound, measured, frac))
+
+
+f64 = P.f64
+
+
+def widened(existing, err32, what):
+    """max(existing, 4 x the f32 restatement's error); a kept bound holds the restatement."""
+    if MARGIN * err32 <= existing:
+        assert err32 <= existing, what
+        return existing
+    return MARGIN * err32
+
+
+def check(got, ref, ref32, rel, what):
+    """|got - ref| <= bound * max|ref|, bound = max(rel, 4 x max|ref32 - ref| / max|ref|)."""
+    got, ref, ref32 = f64(got), f64(ref), f64(ref32)
+    assert got.shape == ref.shape == ref32.shape, (what, got.shape, ref.shape, ref32.shape)
+    scale = ref.abs().max().item()
+    bound = widened(rel, (ref32 - ref).abs().max().item() / scale, what)
+    err = (got - ref).abs().max().item()
+    print("%s: max err %.3e of max|ref|, bound %.3e (existing %.1e)" % (what, err / scale, bound, rel))
+    _note(what, err / (bound * scale), "%.3e max|ref|" % bound, "%.3e max|ref|" % (err / scale))
+    assert err <= bound * scale, "%s: max err %.3e vs scale %.3e (bound %.3e)" % (what, err, scale, bound)
+
+
+def check_stored(got, ref, ref32, rel, what, dt):
+    """A quantity stored in dt: the bound of check(), plus one bf16 rounding (2^-8 |ref|
+    per element) when dt is bf16.  ref32 is the unrounded f32 restatement."""
+    if dt == F32:
+        return check(got, ref, ref32, rel, what)
+    got, ref, ref32 = f64(got), f64(ref), f64(ref32)
+    assert got.shape == ref.shape == ref32.shape, (what, got.shape, ref.shape, ref32.shape)
+    scale = ref.abs().max().item()
+    bound = widened(rel, (ref32 - ref).abs().max().item() / scale, what)
+    allowed = P.BF16_REL * ref.abs() + bound * scale
+    frac = ((got - ref).abs() / allowed).max().item()
+    print("%s: worst element at %.3f of 2^-8|ref| + %.3e max|ref|" % (what, frac, bound))
+    _note(what, frac, "2^-8 |ref| + %.3e max|ref|" % bound, "%.3f of the bound" % frac)
+    assert frac <= 1.0, "%s: worst element at %.3f of its bound (scale %.3e)" % (what, frac, scale)
+
+
+def check_rel(got, ref, ref32, rel, what):
+    """|got - ref| <= bound * |ref| per element, bound = max(rel, 4 x max|ref32 / ref - 1|)."""
+    got, ref, ref32 = f64(got), f64(ref), f64(ref32)
+    assert got.shape == ref.shape == ref32.shape, (what, got.shape, ref.shape, ref32.shape)
+    bound = widened(rel, ((ref32 - ref).abs() / ref.abs()).max().item(), what)
+    frac = ((got - ref).abs() / (bound * ref.abs())).max().item()
+    print("%s: worst element at %.3f of rel %.3e (existing %.1e)" % (what, frac, bound, rel))
+    _note(what, frac, "%.3e |ref|" % bound, "%.3e |ref|" % (frac * bound))
+    assert frac <= 1.0, "%s: worst element at %.3f of rel %.3e" % (what, frac, bound)
+
+
+# the formulas of rowwise_ref.ln_fwd_ref / ln_bwd_ref in a chosen precision
+def ln_fwd_formula(x, y, gamma, beta, eps, keep, scale, dtype):
+    y = y.detach().cpu().to(dtype)
+    s = y * keep.to(dtype) * scale
+    if x is not None:
+        s = s + x.detach().cpu().to(dtype)
+    mean = s.mean(1)
+    var = ((s - mean[:, None]) ** 2).mean(1)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    out = (s - mean[:, None]) * rstd[:, None] * gamma.detach().cpu().to(dtype) + beta.detach().cpu().to(dtype)
+    return s, out, mean, rstd
+
+
+def ln_bwd_formula(s, mean, rstd, g, gamma, dtype):
+    s, g, gamma = s.cpu().to(dtype), g.cpu().to(dtype), gamma.detach().cpu().to(dtype)
+    mean, rstd = mean.cpu().to(dtype)[:, None], rstd.cpu().to(dtype)[:, None]
+    xhat = (s - mean) * rstd
+    gg = g * gamma
+    ds = rstd * (gg - gg.mean(1, keepdim=True) - xhat * (gg * xhat).mean(1, keepdim=True))
+    return ds, (g * xhat).sum(0), g.sum(0)
+
+
+def test_formulas_are_the_reference():
+    """In float64 the restated formulas are rowwise_ref's, bit for bit."""
+    rows, D, dt, n_masks = 5, 384, F32, 2
+    inp = P.ln_inputs(rows, D, dt)
+    keep, scale = R.branch_mask(rows, D, n_masks, LN_P, LN_SEEDS)
+    want = R.ln_fwd_ref(inp["x"], inp["y"], inp["gamma"], inp["beta"], LN_EPS, n_masks, LN_P, LN_SEEDS)
+    got = ln_fwd_formula(inp["x"], inp["y"], inp["gamma"], inp["beta"], LN_EPS, keep, scale, torch.float64)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    g = f64(inp["dout"])
+    wb = R.ln_bwd_ref(want[0], want[2], want[3], g, f64(inp["gamma"]))
+    gb = ln_bwd_formula(want[0], want[2], want[3], g, inp["gamma"], torch.float64)
+    for a, b in zip(gb, wb):
+        assert torch.equal(a, b)
+
+
+def bwd_errors(dt, rows, D, n_masks, g):
+    """The f32 restatement's backward error at this shape, from reference data only: the
+    f64 forward reference rounded to what the forward stores is the input of both the
+    f64 and the f32 formulas.  Returns (f64 results, f32 results) of ds, dgamma, dbeta,
+    dbranch (unrounded), dbranch column sums."""
+    inp = P.ln_inputs(rows, D, dt)
+    keep, scale = R.branch_mask(rows, D, n_masks, LN_P, LN_SEEDS)
+    rs, _, rm, rr = R.ln_fwd_ref(inp["x"], inp["y"], inp["gamma"], inp["beta"], LN_EPS, n_masks, LN_P, LN_SEEDS)
+    s, mean, rstd = rs.to(dt), rm.float(), rr.float()
+    out, stored = [], None
+    for prec in (torch.float64, torch.float32):
+        ds, dg, db = ln_bwd_formula(s, mean, rstd, g, inp["gamma"], prec)
+        dbr = ds * keep.to(prec) * scale
+        if stored is None:
+            stored = dbr.to(dt)  # the column sums are of stored values: the same ones in both precisions
+        out.append((ds, dg, db, dbr, stored.to(prec).sum(0)))
+    return out
+
+
+def shift(ref, pair):
+    """The f32 restatement's error (pair = f64 and f32 results on reference data) carried
+    onto the reference of the check: ref + (f32 - f64)."""
+    return f64(ref) + (f64(pair[1]) - pair[0])
+
+
+def ln_check_backward(dt, rows, D, n_masks, n_part, fwd, got, g, tag):
+    ds, dbr, part = got
+    inp = P.ln_inputs(rows, D, dt)
+    rds, rdg, rdb = R.ln_bwd_ref(f64(fwd["s"][:rows]), f64(fwd["mean"][:rows]), f64(fwd["rstd"][:rows]), g,
+                                 f64(inp["gamma"]))
+    e64, e32 = bwd_errors(dt, rows, D, n_masks, g)
+    n = "%s D=%d%s" % (P.dname(dt), D, tag)
+    check(ds[:rows], rds, shift(rds, (e64[0], e32[0])), 1e-5, "ln_bwd ds " + n)
+    check(f64(part[0, :n_part]).sum(0), rdg, shift(rdg, (e64[1], e32[1])), 1e-5, "ln_bwd dgamma " + n)
+    check(f64(part[1, :n_part]).sum(0), rdb, shift(rdb, (e64[2], e32[2])), 1e-5, "ln_bwd dbeta " + n)
+    if dbr is not None:
+        keep, scale = R.branch_mask(rows, D, n_masks, LN_P, LN_SEEDS)
+        rbr = rds * keep.double() * scale
+        check_stored(dbr[:rows], rbr, shift(rbr, (e64[3], e32[3])), 1e-5, "ln_bwd dbranch " + n, dt)
+        rsum = f64(dbr[:rows]).sum(0)
+        check(f64(part[2, :n_part]).sum(0), rsum, shift(rsum, (e64[4], e32[4])), 1e-5, "ln_bwd dbranch_part " + n)
+
+
+# the three row configurations of test_layernorm_parity, and one that gives every row
+# group of a row-cooperative block several passes (the backward takes 8 rows per pass;
+# at D = 384 a block is 4 row groups: 25 rows each here)
+LN_CFGS = {"rows53_part3": (53, 3), "rows1_part1": (1, 1), "rows53_partmax": (53, (53 + 7) // 8),
+           "rows200_part2": (200, 2)}
+
+
+@pytest.mark.parametrize("cfg", list(LN_CFGS))
+@pytest.mark.parametrize("n_masks", [0, 1, 2])
+@pytest.mark.parametrize("dt", P.DTYPES)
+@pytest.mark.parametrize("D", WIDTHS)
+def test_layernorm_width_parity(D, dt, n_masks, cfg):
+    """Forward (s_out, out, mean, rstd, the keep pattern; with x and with x = NULL) and
+    backward (ds, dgamma, dbeta, dbranch with the hash mask at its position,
+    dbranch_part; ds aliasing dout, dout2, dbranch = NULL).  rows = 53 with 3 partial
+    blocks gives a block (a wave, at D = 768) several rows and the prefetch a partly
+    empty last pass; rows = 1 is the block that must not hang on a barrier; n_part =
+    ceil(rows / 8) is the largest a caller of any width may pass; rows = 200 with 2
+    blocks runs several full passes in every row group.  Nothing is written past rows
+    or past n_part."""
+    rows, n_part = LN_CFGS[cfg]
+    inp = P.ln_inputs(rows, D, dt)
+    keep, scale = R.branch_mask(rows, D, n_masks, LN_P, LN_SEEDS)
+    n = "%s D=%d" % (P.dname(dt), D)
+    fwd = None
+    for with_x in (False, True):
+        o = P.ln_forward(dt, rows, D, n_masks, with_x)
+        x = inp["x"] if with_x else None
+        rs, ro, rm, rr = R.ln_fwd_ref(x, inp["y"], inp["gamma"], inp["beta"], LN_EPS, n_masks, LN_P, LN_SEEDS)
+        s32, o32, m32, r32 = ln_fwd_formula(x, inp["y"], inp["gamma"], inp["beta"], LN_EPS, keep, scale, torch.float32)
+        check_stored(o["s"][:rows], rs, s32, 2e-6, "ln_fwd s_out " + n, dt)
+        check_stored(o["out"][:rows], ro, o32, 2e-6, "ln_fwd out " + n, dt)
+        check(o["mean"][:rows], rm, m32, 2e-6, "ln_fwd mean " + n)
+        check_rel(o["rstd"][:rows], rr, r32, 1e-5, "ln_fwd rstd " + n)
+        branch = f64(o["s"][:rows]) - (f64(x) if with_x else 0.0)
+        assert torch.equal(branch != 0, keep), "keep pattern is not the dropout hash's (with_x=%s)" % with_x
+        fwd = o
+    g = f64(inp["dout"])
+    plain = P.ln_backward(dt, rows, D, n_masks, n_part, fwd)
+    ln_check_backward(dt, rows, D, n_masks, n_part, fwd, plain, g, "")
+    aliased = P.ln_backward(dt, rows, D, n_masks, n_part, fwd, alias=True)
+    assert torch.equal(aliased[0][:rows], plain[0][:rows]), "ds aliasing dout changed ds"
+    assert torch.equal(aliased[1][:rows], plain[1][:rows]), "ds aliasing dout changed dbranch"
+    assert torch.equal(aliased[2][:, :n_part], plain[2][:, :n_part]), "ds aliasing dout changed the partials"
+    with2 = P.ln_backward(dt, rows, D, n_masks, n_part, fwd, dout2=True)
+    ln_check_backward(dt, rows, D, n_masks, n_part, fwd, with2, g + f64(inp["dout2"]), " (dout2)")
+    nobr = P.ln_backward(dt, rows, D, n_masks, n_part, fwd, dbranch=False)
+    assert torch.equal(nobr[0][:rows], plain[0][:rows]), "dbranch = NULL changed ds"
+    assert torch.equal(nobr[2][:2, :n_part], plain[2][:2, :n_part]), "dbranch = NULL changed dgamma / dbeta partials"
+
+
+@pytest.mark.parametrize("dt", P.DTYPES)
+@pytest.mark.parametrize("D", [768, 2048])
+def test_layernorm_width_rot_out(D, dt):
+    """rot_out rotates the stored (rounded) out by position row % rope_T with
+    [rope_T][D/2] tables; the rows cross the period five times."""
+    rows, T, n_masks = 53, 10, 1
+    cs, sn = rotation_tables(T, D, DEV)
+    inp = P.ln_inputs(rows, D, dt)
+    keep, scale = R.branch_mask(rows, D, n_masks, LN_P, LN_SEEDS)
+    o = P.ln_forward(dt, rows, D, n_masks, True, rope=(cs, sn, T))
+    ro = R.ln_fwd_ref(inp["x"], inp["y"], inp["gamma"], inp["beta"], LN_EPS, n_masks, LN_P, LN_SEEDS)[1]
+    o32 = ln_fwd_formula(inp["x"], inp["y"], inp["gamma"], inp["beta"], LN_EPS, keep, scale, torch.float32)[1]
+    n = "%s D=%d" % (P.dname(dt), D)
+    check_stored(o["out"][:rows], ro, o32, 2e-6, "ln_fwd out " + n, dt)
+    # the rotation's own f32 error, on reference data: the rounded reference out
+    base = ro.to(dt)
+    rot64 = R.rope_ref(f64(base), cs, sn, T, D)
+    t = torch.arange(rows) % T
+    c, s = cs.cpu()[t], sn.cpu()[t]
+    b32 = base.float()
+    rot32 = torch.empty_like(b32)
+    rot32[:, 0::2] = b32[:, 0::2] * c - b32[:, 1::2] * s
+    rot32[:, 1::2] = b32[:, 0::2] * s + b32[:, 1::2] * c
+    want = R.rope_ref(f64(o["out"][:rows]), cs, sn, T, D)
+    check_stored(o["rot"][:rows], want, want + (f64(rot32) - rot64), 2e-6, "ln_fwd rot_out " + n, dt)
+
+
+@pytest.mark.parametrize("D", [192, 1000, 2176])
+def test_unsupported_width_is_refused(D):
+    """Any other D returns hipErrorInvalidValue before a launch, with the rule in the message."""
+    inp = dict(y=P.rnd(8, D), gamma=P.rnd(D), beta=P.rnd(D))
+    a = K.LnArgs()
+    a.dtype, a.rows, a.D = K.dtype_code(F32), 8, D
+    a.y, a.gamma, a.beta, a.eps = inp["y"].data_ptr(), inp["gamma"].data_ptr(), inp["beta"].data_ptr(), LN_EPS
+    out, stat = P.nans(8, D), P.nans(2, 8)
+    a.out, a.mean, a.rstd = out.data_ptr(), stat[0].data_ptr(), stat[1].data_ptr()
+    with pytest.raises(RuntimeError, match="multiple of 128"):
+        K.ln_fwd(a)
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()
+
+
+def test_q8_copy_is_refused_at_new_widths():
+    """The e4m3 side copy stays with D in 128 / 256 / 512 / 1024."""
+    D, rows = 768, 8
+    inp = P.ln_inputs(rows, D, BF16)
+    a = P.ln_args(BF16, rows, D, inp, 0)
+    out, stat = P.nans(rows, D, dtype=BF16), P.nans(2, rows)
+    a.out, a.mean, a.rstd = out.data_ptr(), stat[0].data_ptr(), stat[1].data_ptr()
+    q8 = torch.zeros(rows, D, dtype=torch.uint8, device=DEV)
+    sc = P.nans(rows)
+    a.q8, a.ldq8, a.q8_scale = q8.data_ptr(), D, sc.data_ptr()
+    with pytest.raises(RuntimeError, match="128/256/512/1024"):
+        K.ln_fwd(a)
+    torch.cuda.synchronize()
+    assert torch.isnan(out.float()).all() and torch.isnan(sc).all()
