@@ -763,7 +763,9 @@ NSTL_DEV void ring_epi(const GemmParams& p, const ACC& acc, int row0, int col0, 
       csum[e] = sum_xor16(csum[e]);
       csum[e] = sum_xor32(csum[e]);
     }
-    if (lane < LPR && colok) {
+    // a wave whose 128 rows all lie past M has no partial row: colsum_part holds
+    // ceil(M / 128) of them (M % 256 in 1..128: the last tile's lower waves)
+    if (lane < LPR && colok && row0 < p.M) {
       float* dst = p.colsum_part + (int64_t)(row0 >> 7) * p.N + j;
 #pragma unroll
       for (int e = 0; e < CW; ++e)
