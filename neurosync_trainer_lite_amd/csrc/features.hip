@@ -8,7 +8,8 @@
 // drop lag 0, replicate near-silent edge frames.  The windowed frame lives in LDS
 // as f64 (the reference is f64 from the window on); the default kernel
 // (autocorr3_kernel) runs the lag products as a per-frame f64 GEMM on the matrix
-// cores, one wave per frame; the VALU forms below it stay behind switches.
+// cores, one wave per frame; frames whose image does not fit its LDS budget take
+// the VALU form (autocorr2_kernel).
 #include <algorithm>
 #include <cmath>
 #include <deque>
@@ -20,92 +21,18 @@
 #include "status.h"
 
 namespace {
-constexpr int NT = 256;
 constexpr int MAX_FRAME = 4096;
 
-// One workgroup per frame.  Lags 0..n_lags are computed by 24 groups of 8
-// consecutive lags x 10 chunks of the sample index: a thread slides an 8-wide
-// register window along w (two LDS reads per 8 f64 FMAs), chunk partials are
-// summed in LDS.  w is zero-padded past the frame, so sum_{k<L} w[k] w[k+lag]
-// needs no per-lag bound.
-constexpr int AC_LG = 8;      // lags per thread
-constexpr int AC_GROUPS = 24; // lag groups: up to 192 lags (0..n_lags <= 191)
-constexpr int AC_CHUNKS = 10; // sample-index chunks
-
-__global__ __launch_bounds__(NT) void autocorr_kernel(const float* y, int64_t n, int L, int hop, int n_lags,
-                                                       const double* __restrict__ hann, double* out) {
-  __shared__ double w[MAX_FRAME + AC_LG * AC_GROUPS];
-  __shared__ double part[AC_CHUNKS][AC_LG * AC_GROUPS];
-  __shared__ double red[NT / 64];
-  const int f = blockIdx.x, tid = threadIdx.x;
-  const int64_t start = (int64_t)f * hop - L / 2;
-  double s = 0.0;
-  for (int k = tid; k < L; k += NT) {
-    int64_t i = start + k;
-    if (i < 0) i = -i;                       // numpy 'reflect' (edge not repeated)
-    if (i >= n) i = 2 * (n - 1) - i;
-    const double v = (double)y[i];
-    w[k] = v;
-    s += v;
-  }
-  for (int k = L + tid; k < L + AC_LG * AC_GROUPS; k += NT) w[k] = 0.0;
-  s = wave_sum_d(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  const double mean = (red[0] + red[1] + red[2] + red[3]) / L;
-  // the reference subtracts the mean in float32 (frames are float32 until the
-  // float64 window multiplies them)
-  const float mean_f = (float)mean;
-  for (int k = tid; k < L; k += NT) {
-    const float c = (float)w[k] - mean_f;
-    w[k] = (double)c * hann[k];
-  }
-  __syncthreads();
-  if (tid < AC_GROUPS * AC_CHUNKS) {
-    const int g = tid % AC_GROUPS, c = tid / AC_GROUPS;
-    const int l0 = g * AC_LG;
-    const int chunk = (L + AC_CHUNKS - 1) / AC_CHUNKS;
-    const int k0 = c * chunk, k1 = min(L, k0 + chunk);
-    double acc[AC_LG], win[AC_LG];
-#pragma unroll
-    for (int r = 0; r < AC_LG; ++r) {
-      acc[r] = 0.0;
-      win[r] = w[k0 + l0 + r];
-    }
-    for (int k = k0; k < k1; ++k) {
-      const double a = w[k];
-#pragma unroll
-      for (int r = 0; r < AC_LG; ++r) acc[r] = fma(a, win[r], acc[r]);
-#pragma unroll
-      for (int r = 0; r < AC_LG - 1; ++r) win[r] = win[r + 1];
-      win[AC_LG - 1] = w[k + l0 + AC_LG];
-    }
-#pragma unroll
-    for (int r = 0; r < AC_LG; ++r) part[c][l0 + r] = acc[r];
-  }
-  __syncthreads();
-  __shared__ double ac0;
-  for (int lag = tid; lag <= n_lags; lag += NT) {
-    double acc = 0.0;
-#pragma unroll
-    for (int c = 0; c < AC_CHUNKS; ++c) acc += part[c][lag];
-    if (lag == 0) ac0 = acc;
-    if (lag > 0) out[(int64_t)f * n_lags + (lag - 1)] = acc;
-  }
-  __syncthreads();
-  if (ac0 != 0.0)
-    for (int lag = tid; lag < n_lags; lag += NT) out[(int64_t)f * n_lags + lag] /= ac0;
-}
-
-// Register-tiled form (default; NSTL_AUTOCORR_V1=1 keeps the kernel above):
-// a thread owns 16 consecutive lags over one 16-aligned chunk of the sample
+// Register-tiled VALU form, one workgroup per frame (frame lengths past
+// autocorr3_kernel's LDS budget): w is zero-padded past the frame, so
+// sum_{k<L} w[k] w[k+lag] needs no per-lag bound.
+// A thread owns 16 consecutive lags over one 16-aligned chunk of the sample
 // index and, per block of 16 samples, reads a[16] = w[k..k+15] and b[31] =
 // w[k+l0..k+l0+30] from LDS (16-byte reads) for 256 f64 FMAs -- no register
-// shifting (the sliding window above moves 7 registers per 8 FMAs).  12 lag
-// groups x 20 chunks = 240 threads; chunk partials summed in LDS in chunk order.
-// r3: the partials overwrite the frame image once every thread is done with it
-// (one barrier), so a workgroup holds max(frame, partials) = 31 KB of LDS instead
-// of 46 KB (5 workgroups per CU instead of 3), and every thread forms lag 0 from
+// shifting.  12 lag groups x 20 chunks = 240 threads; chunk partials summed in
+// LDS in chunk order.  The partials overwrite the frame image once every thread
+// is done with it (one barrier), so a workgroup holds max(frame, partials) of
+// LDS (35 KB at the longest frame), and every thread forms lag 0 from
 // the same partials in the same order, so the normalisation is one pass over
 // registers instead of a second read-modify-write of the output.
 constexpr int AC2_LG = 16, AC2_GROUPS = 12, AC2_CHUNKS = 20;
@@ -435,7 +362,7 @@ extern "C" int nstl_autocorr(const float* y, int64_t n_samples, int frame_length
                              double* out, int n_frames, void* stream) {
   NSTL_CHECK_ARG(y && out && n_samples > frame_length / 2 && frame_length > 1 && frame_length <= MAX_FRAME,
                  "nstl_autocorr: bad sizes");
-  NSTL_CHECK_ARG(hop_length > 0 && n_lags > 0 && n_lags < frame_length && n_lags < AC_LG * AC_GROUPS,
+  NSTL_CHECK_ARG(hop_length > 0 && n_lags > 0 && n_lags < frame_length && n_lags < AC2_LG * AC2_GROUPS,
                  "nstl_autocorr: bad lags");
   const int64_t padded = n_samples + 2 * (frame_length / 2);
   const int expect = (int)((padded - frame_length) / hop_length + 1);
@@ -443,25 +370,14 @@ extern "C" int nstl_autocorr(const float* y, int64_t n_samples, int frame_length
   hipStream_t st = (hipStream_t)stream;
   const double* hann = nullptr;
   if (int rc = get_hann(frame_length, &hann)) return rc;
-  static const bool v1 = [] {
-    const char* e = getenv("NSTL_AUTOCORR_V1");
-    return e && e[0] == '1';
-  }();
-  static const bool v2 = [] {
-    const char* e = getenv("NSTL_AUTOCORR_V2");
-    return e && e[0] == '1';
-  }();
-  if (!v1 && !v2 && n_lags < 16 * (AC3_TILES - 1) && ac3_lds(frame_length) <= 65536) {
+  if (n_lags < 16 * (AC3_TILES - 1) && ac3_lds(frame_length) <= 65536) {
     hipLaunchKernelGGL(autocorr3_kernel, dim3((n_frames + AC3_WAVES - 1) / AC3_WAVES), dim3(64 * AC3_WAVES),
                        ac3_lds(frame_length), st, y, n_samples, frame_length, hop_length, n_lags, n_frames, hann, out,
                        ac3_xlen(frame_length));
-  } else if (!v1 && n_lags < AC2_LG * AC2_GROUPS && ac2_lds(frame_length) <= 65536) {
+  } else {
     hipLaunchKernelGGL(autocorr2_kernel, dim3(n_frames), dim3(AC2_NT), ac2_lds(frame_length), st, y, n_samples,
                        frame_length, hop_length, n_lags, hann, out, (int)ac2_chunk(frame_length),
                        (int)ac2_wlen(frame_length));
-  } else {
-    hipLaunchKernelGGL(autocorr_kernel, dim3(n_frames), dim3(NT), 0, st, y, n_samples, frame_length, hop_length,
-                       n_lags, hann, out);
   }
   NSTL_LAUNCH_CHECK("nstl_autocorr");
   hipLaunchKernelGGL(autocorr_edges, dim3(1), dim3(256), 0, st, out, n_frames, n_lags);
@@ -1141,21 +1057,13 @@ __global__ void init_key(int* k) { *k = 0; }  // mel power >= 0: bits of 0.f
 // The autocorrelation depends on the audio only, so nstl_features forks it onto a
 // side stream (one per device, created once) and joins before the lag reduction:
 // the f64-MFMA-bound autocorrelation runs beside the latency-bound STFT/mel, DCT
-// and CMVN chain instead of after it.  NSTL_FEATURES_FORK=0 keeps one stream.
+// and CMVN chain instead of after it.
 struct FeatFork {
   int dev = -1;
   hipStream_t side = nullptr;
   hipEvent_t fork = nullptr, join = nullptr;
 };
 std::mutex g_fork_mu;  // held from the fork record to the join wait of one call
-
-bool fork_on() {
-  static const bool on = [] {
-    const char* e = getenv("NSTL_FEATURES_FORK");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
 
 // caller holds g_fork_mu
 FeatFork* get_fork() {
@@ -1174,16 +1082,9 @@ FeatFork* get_fork() {
   return &forks.back();
 }
 
-// NSTL_FEATURES_FFT=0: the frames -> DFT GEMM -> power -> mel GEMM path instead
-// of the fused STFT/mel kernel (A/B comparisons; also any n_fft with a prime
-// factor > 7)
-bool use_fft(const FeatTables* T) {
-  static const int on = [] {
-    const char* e = getenv("NSTL_FEATURES_FFT");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
-  return on && T->nf > 0;
-}
+// an n_fft with a prime factor > 7 has no FFT plan: it takes the frames -> DFT GEMM
+// -> power -> mel GEMM path instead of the fused STFT/mel kernel
+bool use_fft(const FeatTables* T) { return T->nf > 0; }
 
 int launch_stft_mel(const FeatTables* T, const float* y, int64_t n_samples, int hop, int F, float* mel, int* key,
                     hipStream_t st) {
@@ -1191,11 +1092,7 @@ int launch_stft_mel(const FeatTables* T, const float* y, int64_t n_samples, int 
   plan.n = T->n_fft;
   plan.nf = T->nf;
   for (int i = 0; i < 16; ++i) plan.radix[i] = T->radix[i];
-  static const bool wg_form = [] {
-    const char* e = getenv("NSTL_STFT_WG");
-    return e && e[0] == '1';
-  }();
-  if (!wg_form && T->n_fft <= SW_MAXN && n_samples < (int64_t)1 << 29) {
+  if (T->n_fft <= SW_MAXN && n_samples < (int64_t)1 << 29) {
     const size_t lw = stft_wave_lds(T->n_fft, T->nnz);
     int dev = 0, cus = 0, per_cu = 0;
     if (hipFuncSetAttribute((const void*)stft_mel_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1262,12 +1159,8 @@ extern "C" int nstl_features(const float* y, int64_t n_samples, int sr, float* o
   float* mf = (float*)(ws + L.mfcc);
   double* ac = (double*)(ws + L.ac);
   int* key = (int*)(ws + L.key);
-  std::unique_lock<std::mutex> fork_lk(g_fork_mu, std::defer_lock);
-  FeatFork* fk = nullptr;
-  if (fork_on()) {
-    fork_lk.lock();
-    fk = get_fork();
-  }
+  std::lock_guard<std::mutex> fork_lk(g_fork_mu);
+  FeatFork* const fk = get_fork();  // nullptr: one stream
   // Once the side stream is forked, every return joins it first: the side stream
   // reads y and writes the workspace, and the caller's allocator may hand those
   // blocks out again on st as soon as st has passed its last use of them.

@@ -41,9 +41,8 @@ struct GemmParams {
   const char* aux; int64_t ld_aux; int aux_f32;
   float inv_keep; uint32_t thresh; uint64_t seed;
   const float* rope_cos; const float* rope_sin; int rope_T, rope_dim, rope_cols;
-  int rope_fast;  // ring epilogue: cos/sin recomputed from t * inv_freq instead of read from the tables
   float* ws;
-  int debug_skip_epilogue; int k_chunk;  // split-K: partial slabs [z][M][N]
+  int k_chunk;  // split-K: partial slabs [z][M][N]
   float* colsum_part;  // [ceil(M/128)][N]: column sums of C as stored (dReLU ring epilogue)
   uint64_t* relu_mask;  // ReLU-dropout keep&positive bits, ring epilogue layout (relu_mask_index)
   const float* a_scale; const float* b_scale;  // fp8: row scales of A [M] and of B [N]
@@ -536,10 +535,6 @@ NSTL_DEV void ring_epi(const GemmParams& p, const ACC& acc, int row0, int col0, 
   // a pass's rows ib + it * RPI span < 64 rows: with rope_T >= 64 their positions
   // follow from the pass's first by one conditional wrap (no integer modulo per row)
   const bool rope_tinc = EM == EM_ROPE && p.rope_T >= 64;
-  float rope_if[4];  // inv_freq of this lane's 4 rotation pairs (NSTL_GEMM_ROPE=fast)
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    rope_if[e] = EM == EM_ROPE ? expf(-9.21034049987793f * (float)(2 * (rope_pr + e)) / (float)p.rope_dim) : 0.f;
   const int r0 = lane / LPR;
   // dReLU epilogue: column sums of the stored dh (the FFN1 bias gradient)
   const bool csum_on = EM == EM_DRELU && p.colsum_part != nullptr;
@@ -581,18 +576,7 @@ NSTL_DEV void ring_epi(const GemmParams& p, const ACC& acc, int row0, int col0, 
           } else {
             t = i % p.rope_T;
           }
-          if (rope_vec && p.rope_fast) {
-            // angle = f32(t) * inv_freq with inv_freq = expf(-ln(1e4) * 2i / d), which is
-            // NOT the tables' pow form, then the hardware sin / cos, which lose accuracy as
-            // the angle grows: only a kernel-level tolerance covers this (off by default;
-            // it needs a parity test against the tables at the largest production T first)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float a = (float)t * rope_if[e];
-              sn[e] = __sinf(a);
-              cs[e] = __cosf(a);
-            }
-          } else if (rope_vec) {
+          if (rope_vec) {
             cs = *(const f32x4*)(p.rope_cos + t * rhalf + rope_pr);
             sn = *(const f32x4*)(p.rope_sin + t * rhalf + rope_pr);
           } else {
@@ -718,8 +702,7 @@ NSTL_DEV void ring_epi(const GemmParams& p, const ACC& acc, int row0, int col0, 
           }
         }
         char* dst = C + ((int64_t)i * ldc + j) * ESZ;
-        if (p.debug_skip_epilogue == 2) {  // NSTL_GEMM_DEBUG=skip_store: timing experiments only
-        } else if (vec) {
+        if (vec) {
           if (ESZ == 4)
             *(f32x4*)dst = (f32x4){v[0], v[1 % CW], v[2 % CW], v[3 % CW]};
           else
@@ -833,8 +816,7 @@ NSTL_DEV void ring_epi_bf16_direct_b(const GemmParams& p, const f32x4 (&acc)[8][
       const auto s0 = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
       const auto s1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
       const int col = 16 * (bp + odd) + 4 * (g - odd);
-      if (p.debug_skip_epilogue != 2)
-        *(uint4*)(crow + col) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+      *(uint4*)(crow + col) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
     }
   }
 }
@@ -842,30 +824,10 @@ NSTL_DEV void ring_epi_bf16_direct_b(const GemmParams& p, const f32x4 (&acc)[8][
 constexpr int R_SMEM = R_STAGES * R_SLOT;
 static_assert(8 * RING_EPI_WAVE <= R_SMEM, "epilogue scratch must fit in the ring");
 
-// Diagnostic build only (make stamps -> libnstl_hip_stamps.so, tools/gemm_timeline.py):
-// wave 0 of every ring-GEMM workgroup records the global 100 MHz clock at tile
-// entry, after the prologue, after the K loop and after its epilogue stores have
-// retired, plus where it ran (HW_ID, XCC_ID).  No product build executes a stamp.
-#ifdef NSTL_STAMPS
-constexpr int STAMP_MAX = 1 << 16, STAMP_W = 8;
-__device__ unsigned long long g_nstl_stamps[STAMP_MAX * STAMP_W];
-NSTL_DEV unsigned long long rt_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define NSTL_STAMP(var) const unsigned long long var = rt_stamp()
-#else
-#define NSTL_STAMP(var)
-#endif
-
 // One 256 x 256 output tile of p: `id` is the tile's linear index in p's grid
 // (already XCD-remapped by the caller), `kz` its split-K chunk.
 template <bool AK, bool BKM, int EM>
 NSTL_DEV void ring_tile(const GemmParams& p, int id, int kz0, int kz1, char* smem) {
-  NSTL_STAMP(st_entry);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -897,7 +859,6 @@ NSTL_DEV void ring_tile(const GemmParams& p, int id, int kz0, int kz1, char* sme
   else if (nk == 2) NSTL_VMCNT(4);
   else NSTL_VMCNT(0);
   __builtin_amdgcn_s_barrier();
-  NSTL_STAMP(st_prologue);
   if (wm == 1) __builtin_amdgcn_s_barrier();  // the stagger
 
   // Branch-free steps (as the fp8 kernel): in the main loop both groups wait
@@ -960,13 +921,7 @@ NSTL_DEV void ring_tile(const GemmParams& p, int id, int kz0, int kz1, char* sme
     for (int kt = 0; kt < nk; ++kt) step(kt, false, -1);
   }
   if (wm == 0) __builtin_amdgcn_s_barrier();  // close the stagger
-  NSTL_STAMP(st_kloop);
-  if (p.debug_skip_epilogue == 1) {  // timing experiments only (NSTL_GEMM_DEBUG=skip_epi)
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) asm volatile("" ::"v"(acc[a][b]));
-  } else if (EM == EM_BF16 && p.direct_epi && m0 + BIG <= p.M && n0 + BIG <= p.N) {
+  if (EM == EM_BF16 && p.direct_epi && m0 + BIG <= p.M && n0 + BIG <= p.N) {
     ring_epi_bf16_direct(p, acc, m0 + wm * 128, n0 + wn * 64, lane);
   } else {
     __syncthreads();  // every wave is done with the ring: it becomes scratch
@@ -975,19 +930,6 @@ NSTL_DEV void ring_tile(const GemmParams& p, int id, int kz0, int kz1, char* sme
     if (EM == EM_GENERIC) ring_epi_generic(p, acc, row0, col0, lane, scr);
     else ring_epi<EM, false>(p, acc, row0, col0, lane, scr, id * 8 + wave);
   }
-#ifdef NSTL_STAMPS
-  NSTL_VMCNT(0);
-  NSTL_STAMP(st_epi);
-  if (wave == 0 && lane == 0) {
-    // slot: tile id (+ 2^15 for the second piece of a split tile)
-    const int slot = (id + blockIdx.y * gridDim.x + (kz0 > 0 && blockIdx.y == 0 ? 32768 : 0)) % STAMP_MAX;
-    unsigned long long* s = g_nstl_stamps + (int64_t)slot * STAMP_W;
-    s[0] = st_entry; s[1] = st_prologue; s[2] = st_kloop; s[3] = st_epi;
-    s[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-    s[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-    s[6] = id; s[7] = nk;
-  }
-#endif
 }
 
 template <bool AK, bool BKM, int EM>
@@ -1140,13 +1082,6 @@ NSTL_DEV void ring_tile_f8(const GemmParams& p, int id, char* smem) {
     for (int kt = 0; kt < nk; ++kt) step(kt, false, -1);
   }
   if (wm == 0) __builtin_amdgcn_s_barrier();  // close the stagger
-  if (p.debug_skip_epilogue == 1) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) asm volatile("" ::"v"(acc[a][b]));
-    return;
-  }
   __syncthreads();  // every wave is done with the ring: it becomes scratch
   char* scr = smem + wave * RING_EPI_WAVE;
   ring_epi<EM, true>(p, acc, m0 + wm * 128, n0 + wn * 64, lane, scr);
@@ -1241,25 +1176,6 @@ int launch_typed(const nstl_gemm_args* a, GemmParams& p, int splits, hipStream_t
   return 0;
 }
 
-// NSTL_GEMM_DEBUG=skip_epi / skip_store: the ring kernel computes no epilogue /
-// stores nothing (timing experiments only: wrong results)
-int getenv_debug_skip_epi() {
-  static const int v = [] {
-    const char* e = getenv("NSTL_GEMM_DEBUG");
-    return !e ? 0 : std::string(e) == "skip_epi" ? 1 : std::string(e) == "skip_store" ? 2 : 0;
-  }();
-  return v;
-}
-
-// NSTL_GEMM_SMALL=1 forces the 128x128 kernel (A/B comparisons, debugging)
-bool getenv_small_gemm() {
-  static const int v = [] {
-    const char* e = getenv("NSTL_GEMM_SMALL");
-    return e && e[0] == '1' ? 1 : 0;
-  }();
-  return v != 0;
-}
-
 }  // namespace
 
 extern "C" int64_t nstl_gemm_workspace_bytes(int M, int N, int split_k) {
@@ -1312,21 +1228,9 @@ int make_params(const nstl_gemm_args* a, GemmParams& p) {
   p.seed = a->seed;
   p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin;
   p.rope_T = a->rope_T; p.rope_dim = a->rope_dim; p.rope_cols = a->rope_cols;
-  {
-    // NSTL_GEMM_ROPE=fast (A/B, read per call): the bf16 ring epilogue recomputes the
-    // RoPE angles (v_sin / v_cos, as the attention backward does) instead of loading
-    // 2 x 16 B of table per row; the f32 parity-mode kernels always use the tables
-    const char* e = getenv("NSTL_GEMM_ROPE");
-    p.rope_fast = e != nullptr && strcmp(e, "fast") == 0;
-  }
   p.ws = nullptr;
-  p.debug_skip_epilogue = getenv_debug_skip_epi();
-  // NSTL_GEMM_DIRECT=0: the LDS-staged EM_BF16 epilogue (A/B; read per call).  The
-  // direct one needs 16-byte aligned rows of C.
-  {
-    const char* e = getenv("NSTL_GEMM_DIRECT");
-    p.direct_epi = !(e && e[0] == '0') && (a->ldc % 8) == 0 && ((uintptr_t)a->C % 16) == 0;
-  }
+  // the direct EM_BF16 epilogue needs 16-byte aligned rows of C
+  p.direct_epi = (a->ldc % 8) == 0 && ((uintptr_t)a->C % 16) == 0;
   p.k_chunk = a->K;
   p.colsum_part = a->colsum_part;
   p.relu_mask = a->relu_mask;
@@ -1378,8 +1282,7 @@ int gemm_f8(const nstl_gemm_args* a, GemmParams& p, hipStream_t st) {
 
 bool big_ok(const nstl_gemm_args* a) {
   const int64_t big_tiles = (int64_t)((a->M + BIG - 1) / BIG) * ((a->N + BIG - 1) / BIG);
-  return a->dtype == NSTL_BF16 && a->K % 64 == 0 && a->M >= BIG && a->N >= BIG && big_tiles >= 32 &&
-         !getenv_small_gemm();
+  return a->dtype == NSTL_BF16 && a->K % 64 == 0 && a->M >= BIG && a->N >= BIG && big_tiles >= 32;
 }
 
 }  // namespace
@@ -1508,16 +1411,3 @@ extern "C" int64_t nstl_gemm_relu_mask_words(const nstl_gemm_args* a) {
   if (em != EM_RELU_DROP && em != EM_DRELU) return 0;
   return (int64_t)((a->M + 63) / 64) * 8 * ((a->N + 7) / 8);
 }
-
-#ifdef NSTL_STAMPS
-// diagnostic build only (not declared in include/nstl.h): copy / clear the stamps
-extern "C" int nstl_debug_gemm_stamps(unsigned long long* host, int64_t n) {
-  n = std::min<int64_t>(n, (int64_t)STAMP_MAX * STAMP_W);
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_nstl_stamps), n * 8, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
-}
-extern "C" int nstl_debug_gemm_stamps_clear() {
-  void* p = nullptr;
-  if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_nstl_stamps)) != hipSuccess) return 1;
-  return hipMemset(p, 0, sizeof(unsigned long long) * STAMP_MAX * STAMP_W) == hipSuccess ? 0 : 1;
-}
-#endif

@@ -796,40 +796,26 @@ __global__ __launch_bounds__(NTR) void ln_bwd_kernel_rc(LnParams p) {
   if (p.dyp) storeG<float, CB>(p.dyp + o, dyb);
 }
 
-// NSTL_LN_G8=0: four-column lane groups (8-byte bf16 accesses) when D % 512 == 0
-bool ln_g8() {
-  static const int v = [] {
-    const char* e = getenv("NSTL_LN_G8");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
-  return v != 0;
-}
-
-// forward at 1024 < D <= 2048, D % 256 == 0: V = D / 64 columns per lane
+// forward at 1024 < D <= 2048, D % 256 == 0: V = D / 64 columns per lane, in lane
+// groups of eight columns (16-byte bf16 accesses) when D % 512 == 0, else of four
 template <typename T, int V>
 void launch_fwd_il(const LnParams& p, int grid, hipStream_t st) {
-  if constexpr (V % 8 == 0) {
-    if (ln_g8()) {
-      hipLaunchKernelGGL((ln_fwd_kernel_il<T, V, 8>), dim3(grid), dim3(NT), 0, st, p);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((ln_fwd_kernel_il<T, V, 4>), dim3(grid), dim3(NT), 0, st, p);
+  hipLaunchKernelGGL((ln_fwd_kernel_il<T, V, (V % 8 == 0 ? 8 : 4)>), dim3(grid), dim3(NT), 0, st, p);
 }
 
 template <typename T, bool BWD>
 int dispatch(const LnParams& p, int grid, hipStream_t st) {
 #define NSTL_LN_CASE(V)                                                                     \
   case V:                                                                                   \
-    if (BWD && V % 8 == 0 && ln_g8())                                                       \
+    if (BWD && V % 8 == 0)                                                                  \
       hipLaunchKernelGGL((ln_bwd_kernel_il<T, (V % 8 == 0 ? V : 8), 8>), dim3(grid), dim3(NTB), 0, st, p); \
     else if (BWD && V % 4 == 0)                                                             \
-      hipLaunchKernelGGL((ln_bwd_kernel_il<T, (V % 4 == 0 ? V : 4), 4>), dim3(grid), dim3(NTB), 0, st, p); \
+      hipLaunchKernelGGL((ln_bwd_kernel_il<T, (V % 8 == 4 ? V : 4), 4>), dim3(grid), dim3(NTB), 0, st, p); \
     else if (BWD) hipLaunchKernelGGL((ln_bwd_kernel<T, V>), dim3(grid), dim3(NT), 0, st, p); \
-    else if (V % 8 == 0 && ln_g8())                                                         \
+    else if (V % 8 == 0)                                                                    \
       hipLaunchKernelGGL((ln_fwd_kernel_il<T, (V % 8 == 0 ? V : 8), 8>), dim3(grid), dim3(NT), 0, st, p); \
     else if (V % 4 == 0)                                                                    \
-      hipLaunchKernelGGL((ln_fwd_kernel_il<T, (V % 4 == 0 ? V : 4), 4>), dim3(grid), dim3(NT), 0, st, p); \
+      hipLaunchKernelGGL((ln_fwd_kernel_il<T, (V % 8 == 4 ? V : 4), 4>), dim3(grid), dim3(NT), 0, st, p); \
     else hipLaunchKernelGGL((ln_fwd_kernel<T, V>), dim3(grid), dim3(NT), 0, st, p);        \
     break;
   switch (p.D / 64) {

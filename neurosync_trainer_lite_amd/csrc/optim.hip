@@ -479,11 +479,7 @@ extern "C" int nstl_adam_step(const nstl_adam_args* a, void* stream) {
   // unrolled +4-8 %, tools/bench_adam.py), strided by the grid
   if (a->coef) {
     NSTL_CHECK_ARG(!a->sumsq_partial, "nstl_adam_step: coef and sumsq_partial are exclusive");
-    // NSTL_ADAM_GRID: cap on its workgroups (how many CUs a range update shares)
-    static const int cap = [] {
-      const char* e = getenv("NSTL_ADAM_GRID");
-      return e ? std::max(1, atoi(e)) : 8192;
-    }();
+    constexpr int cap = 8192;  // its workgroups (how many CUs a range update shares)
     // NSTL_ADAM_NT=0: plain loads / stores (A/B; read per call).  Nontemporal is the
     // default: +0.4 % step rate same-box (586.7k vs 584.3k frames/s, 3 reps)
     const char* ne = getenv("NSTL_ADAM_NT");

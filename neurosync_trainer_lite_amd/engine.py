@@ -41,13 +41,6 @@ def rotation_tables(seq_len, dim, device):
     return torch.cos(angle).contiguous().to(device), torch.sin(angle).contiguous().to(device)
 
 
-def _span(t):
-    """Byte range [lo, hi) a (possibly strided 2-D) view covers."""
-    lo = t.data_ptr()
-    n = 1 + sum((d - 1) * st for d, st in zip(t.shape, t.stride())) if t.numel() else 0
-    return lo, lo + n * t.element_size()
-
-
 ARENA_ALIGN = 64 * 840
 # encoder layers whose weight gradients share one grouped GEMM: 4 x 192 tiles of
 # 256^2 = 768 = three full rounds on 256 CUs (one layer alone: 0.75 of a round)
@@ -160,8 +153,8 @@ class _Buffers:
             self.e_mask = [e(nw, dtype=torch.int64) for _ in range(L)]
             self.d_mask = [e(nw, dtype=torch.int64) for _ in range(L)]
             self.d_maskc = [e(nw, dtype=torch.int64) for _ in range(L)]
-            # LN backward blocks (8 waves each, >= 1 row per wave); NSTL_LN_PARTS: A/B only
-            self.n_part = max(1, min(int(os.environ.get("NSTL_LN_PARTS", "256")), M // 8))
+            # LN backward blocks (8 waves each, >= 1 row per wave)
+            self.n_part = max(1, min(256, M // 8))
             # one per LayerNorm of a layer (3 in a decoder layer): batched reduction
             self.ln_parts = [e(3, self.n_part, D, dtype=f32) for _ in range(3)]
             self.ln_part = self.ln_parts[0]
@@ -210,33 +203,17 @@ class Seq2SeqEngine:
         self.grad_reducer = None   # parallel.GradAllReducer when data-parallel
         self.grad_scale_t = None   # device f32 [1]: loss-gradient pre-scale (1/world)
         self.seed_salt = 0         # data-parallel rank: distinct dropout streams per replica
-        # NSTL_DW_STREAM=1: weight-gradient GEMMs run on a second HIP stream beside
-        # the dX chain.  Off by default: +0.5 % step rate at the 228M config (424.3k
-        # vs 422.3k frames/s), while the per-launch GEMM timing then overlaps.
-        self.dw_stream_on = os.environ.get("NSTL_DW_STREAM", "0") == "1"
-        self._side = None          # torch.cuda.Stream for dW (+ bias colsum)
-        self._side_reads = []      # (lo, hi, event): bytes a queued dW still reads
         # NSTL_DW_GROUP=0: one GEMM per weight gradient (split-K) instead of one
         # grouped launch per decoder layer (its 7 weight gradients are 256 tiles)
         # and per ENC_GROUP encoder layers (4 x 4 weight gradients, 768 tiles)
         self.dw_group_on = os.environ.get("NSTL_DW_GROUP", "1") != "0"
         self._defer = None         # weight-gradient jobs of the current decoder layer
-        # NSTL_FUSED_BIAS=0: q/k/v and FFN1 bias gradients by colsum() instead of
-        # the attention-backward / dReLU-epilogue column sums
-        self.fused_bias_on = os.environ.get("NSTL_FUSED_BIAS", "1") != "0"
-        # NSTL_RES_HANDOFF=0: input gradients of the Linears fed by a LayerNorm are
-        # accumulated into the f32 residual gradient by the GEMM (read-modify-write)
-        # instead of being written in the compute dtype and added by the next LN backward
-        self.res_handoff_on = os.environ.get("NSTL_RES_HANDOFF", "1") != "0"
-        self._dadd_pending = False
+        self._dadd_pending = False  # bb.dadd holds a Linear's input gradient for the next LN backward
         # NSTL_DMEM_CONCAT=0: the memory gradient accumulated into the f32 dmem by one
         # K = 2D GEMM per decoder layer instead of one K = L * 2D GEMM after the decoder
         self.dmem_concat = os.environ.get("NSTL_DMEM_CONCAT", "1") != "0"
         self._wkv = None           # [W_kv_0; ...; W_kv_{L-1}] slab (_kv_weights)
         self._kv_all_done = False  # decode(): every layer's cross k|v projected in one launch
-        # NSTL_RELU_MASK=0: the FFN2 dX epilogue reads the saved hidden h for its
-        # dReLU instead of the 1-bit keep&positive mask the FFN1 epilogue writes
-        self.relu_mask_on = os.environ.get("NSTL_RELU_MASK", "1") != "0"
         # NSTL_REDUCE_BATCH=0: each LayerNorm / bias-gradient partial reduction is
         # its own launch instead of one batched launch per backward layer
         self.reduce_batch_on = os.environ.get("NSTL_REDUCE_BATCH", "1") != "0"
@@ -761,8 +738,7 @@ class Seq2SeqEngine:
             x, sx = xq
             W = qw
             kw.update(a_scale=sx, b_scale=sw)
-        use = relu_mask is not None and self.relu_mask_on and \
-            0 < K.gemm_relu_mask_words(x, W, out, m, n, k, **kw) <= relu_mask.numel()
+        use = relu_mask is not None and 0 < K.gemm_relu_mask_words(x, W, out, m, n, k, **kw) <= relu_mask.numel()
         K.gemm(x, W, out, m, n, k, relu_mask=relu_mask if use else None, stream=self.st, **kw)
         return use
 
@@ -782,12 +758,10 @@ class Seq2SeqEngine:
         if ".transformer_" in wname:
             self._sq_ok = False  # a layer weight gradient without the grouped epilogue's partials
         s = self.splits(n, k, m)
-        st = self._side_begin()
-        K.gemm(dy, x, G, n, k, m, a_kmajor=False, b_kmajor=False, beta=bf, split_k=s, workspace=ws, stream=st)
+        K.gemm(dy, x, G, n, k, m, a_kmajor=False, b_kmajor=False, beta=bf, split_k=s, workspace=ws, stream=self.st)
         if bias:
             bname = wname.replace(".weight", ".bias")
-            K.colsum(dy, dy.stride(0), m, n, self.cur.col_part, self.gb(bname, rows), bf, stream=st)
-        self._side_end(dy)
+            K.colsum(dy, dy.stride(0), m, n, self.cur.col_part, self.gb(bname, rows), bf, stream=self.st)
 
     def _dw_flush(self, ws):
         """Launch the queued weight gradients: one grouped GEMM (no split-K) when
@@ -813,46 +787,6 @@ class Seq2SeqEngine:
             K.gemm(dy, x, G, n, k, m, a_kmajor=False, b_kmajor=False, beta=bf, split_k=self.splits(n, k, m),
                    workspace=ws, stream=self.st)
 
-    # ---------------------------------------------------- side (dW) stream
-    # A dW GEMM only reads dy (a backward scratch buffer) and a saved activation
-    # and only writes its own gradient slice, the split-K workspace and the
-    # colsum partials (all private to the side stream).  So it may run beside
-    # the dX chain: it waits for the main stream at launch (dy is ready), and
-    # the main stream waits for it only before overwriting that dy buffer.
-    def _side_begin(self):
-        if self._side is None:
-            return self.st
-        ev = torch.cuda.Event()
-        ev.record(self._main)
-        self._side.wait_event(ev)
-        return self._side.cuda_stream
-
-    def _side_end(self, dy):
-        if self._side is None:
-            return
-        ev = torch.cuda.Event()
-        ev.record(self._side)
-        lo, hi = _span(dy)
-        self._side_reads.append((lo, hi, ev))
-
-    def _guard(self, *outs):
-        """The main stream is about to write `outs`: wait for dW reads of them."""
-        if not self._side_reads:
-            return
-        spans = [_span(t) for t in outs if t is not None]
-        keep = []
-        for lo, hi, ev in self._side_reads:
-            if any(lo < h and l < hi for l, h in spans):
-                self._main.wait_event(ev)
-            else:
-                keep.append((lo, hi, ev))
-        self._side_reads = keep
-
-    def _side_join(self):
-        if self._side is not None:
-            self._main.wait_stream(self._side)
-            self._side_reads = []
-
     def _dx(self, dy, wname, rows, out, beta, epi=K.EPI_NONE, aux=None, p_drop=0.0, colsum=None, relu_mask=None,
             dyq=None):
         """out (+)= dy W  (W: [N][K] read as [r][j]).  colsum = (partials, grad(b), beta):
@@ -861,7 +795,6 @@ class Seq2SeqEngine:
         `dyq` = (e4m3 dy, row scales): the fp8 form, on W^T's e4m3 copy."""
         W = self.w(wname, rows)
         n, k = W.shape
-        self._guard(out)
         kw = dict(a_kmajor=True, b_kmajor=False, beta=beta, epilogue=epi, aux=aux,
                   ld_aux=aux.stride(0) if aux is not None else 0, p_drop=p_drop)
         if dyq is not None:
@@ -875,7 +808,7 @@ class Seq2SeqEngine:
                 <= relu_mask.numel():
             kw["relu_mask"] = relu_mask
         m = dy.shape[0]
-        nrows = K.gemm_colsum_rows(dy, W, out, m, k, n, **kw) if colsum is not None and self.fused_bias_on else 0
+        nrows = K.gemm_colsum_rows(dy, W, out, m, k, n, **kw) if colsum is not None else 0
         fused = 0 < nrows <= (colsum[0].shape[0] if colsum is not None else 0)
         K.gemm(dy, W, out, m, k, n, colsum_part=colsum[0] if fused else None, stream=self.st, **kw)
         if fused:
@@ -883,12 +816,12 @@ class Seq2SeqEngine:
         return fused
 
     def _dx_res(self, dy, wname, rows, last=False):
-        """Input gradient of a Linear whose input is a LayerNorm output: accumulate
-        it into the f32 residual gradient.  Handoff mode writes it in the compute
-        dtype (as the reference's autocast rounds it) for the next LN backward to
-        add; `last` (the consumer is not an LN backward) keeps the f32 accumulate."""
+        """Input gradient of a Linear whose input is a LayerNorm output, a term of the
+        f32 residual gradient: written in the compute dtype (as the reference's
+        autocast rounds it) for the next LN backward to add; `last` (the consumer is
+        not an LN backward): accumulated into the f32 residual gradient by the GEMM."""
         bb = self.cur
-        if self.res_handoff_on and not last:
+        if not last:
             assert not self._dadd_pending
             self._dx(dy, wname, rows, bb.dadd, 0.0)
             self._dadd_pending = True
@@ -928,7 +861,6 @@ class Seq2SeqEngine:
         a.seed1, a.seed2 = seeds
         a.gamma, a.beta, a.eps = self.b(prefix + ".weight").data_ptr(), self.b(prefix + ".bias").data_ptr(), 1e-5
         a.mean, a.rstd = stats[0].data_ptr(), stats[1].data_ptr()
-        self._guard(dbranch)
         a.s_in, a.dout, a.ds, a.dbranch = s_in.data_ptr(), dres_in.data_ptr(), dres_out.data_ptr(), K.ptr(dbranch)
         if self._dadd_pending:
             a.dout2 = bb.dadd.data_ptr()
@@ -973,11 +905,10 @@ class Seq2SeqEngine:
         if self._red is not None:
             part = self.cur.abias_slots[self._ab_slot]
             self._ab_slot += 1
-        rows = K.attn_bias_rows(a) if bias and self.fused_bias_on else 0
+        rows = K.attn_bias_rows(a) if bias else 0
         fused = 0 < rows <= part.shape[0]
         if fused:
             K.attn_set(a, dbias_part=part)
-        self._guard(dq, dk, dv)
         K.attn_bwd(a, stream=self.st)
         for off, n, out in (bias if fused else ()):
             self._reduce(part[:, off:], part.stride(0), rows, n, out, bf)
@@ -1175,12 +1106,7 @@ class Seq2SeqEngine:
         self.ensure_bound(versions=False)
         self.sync_pending()
         self.cur = bb
-        self._main = torch.cuda.current_stream(self.device)
-        self.st = self._main.cuda_stream
-        if self.dw_stream_on and self._side is None:
-            from .parallel import side_stream
-            self._side = side_stream(self.device)
-        self._side_reads = []
+        self.st = torch.cuda.current_stream(self.device).cuda_stream
         self.p, self.base_seed = sv["p"], sv["seed"]
         self._dadd_pending = False
         self._red = None
@@ -1202,7 +1128,7 @@ class Seq2SeqEngine:
         red = self.grad_reducer
         if red is not None:
             red.begin(self.grads_fresh)
-        ready = (lambda name: self._ready(red, self.end_of[name])) if red is not None else (lambda name: None)
+        ready = (lambda name: red.ready(self.end_of[name])) if red is not None else (lambda name: None)
         dpred = bb.dpred[:, :self.out_dim]
         self._dw(dpred, bb.xf, "decoder.fc_output.weight", 1, bf, ws)
         K.gemm(bb.dpred, self.w("decoder.fc_output.weight"), dres, M, D, self.out_dim, a_kmajor=True,
@@ -1234,7 +1160,7 @@ class Seq2SeqEngine:
         self._ln_bwd(x_last, bb.encf_stats, "encoder.layer_norm", bb.dmem, dres, None, 0, (0, 0), bf)
         ready("encoder.layer_norm.bias")
         # encoder weight gradients: one grouped launch per ENC_GROUP layers
-        enc_group = self.dw_group_on and self._side is None
+        enc_group = self.dw_group_on
         for l in reversed(range(L)):
             if enc_group and self._defer is None:
                 self._defer = []
@@ -1246,10 +1172,8 @@ class Seq2SeqEngine:
             if not enc_group or l % ENC_GROUP == 0:
                 ready("encoder.transformer_encoder.%d.self_attn.v_linear.bias" % l)
         # embedding + global PE: x0 = GPE(src W^T + b)
-        self._guard(bb.demb)
         K.rope(dres, D, bb.demb, D, M, D, cs, sn, T, D, inverse=True, stream=self.st)
         self._dw(bb.demb, sv["x_src"], "encoder.embedding.weight", 1, bf, ws)
-        self._side_join()
         if red is not None:
             red.finish()
         self.grads_fresh = False
@@ -1274,16 +1198,6 @@ class Seq2SeqEngine:
         """The gradient arena was written after backward: the epilogue partials no
         longer describe it (the next clip norm re-reads the arena)."""
         self.sq_state = None
-
-    def _ready(self, red, upto):
-        """Gradient arena prefix final: its all-reduce is ordered after both streams
-        (the side stream waits for the main one and the collective follows it)."""
-        if self._side is None:
-            red.ready(upto)
-            return
-        self._side_begin()
-        with torch.cuda.stream(self._side):
-            red.ready(upto)
 
     def _attn_block_bwd(self, bb, pre, x_in, qkv, o, lse, st, s1, norm, seeds, T, bf, mask, last=False,
                         dy=None, dqkv=None):
@@ -1337,7 +1251,7 @@ class Seq2SeqEngine:
         sd = lambda s: _seed(self.base_seed, False, l, s)
         st = bb.d_stats[l]
         x_in = bb.xdec0 if l == 0 else bb.d_x3[l - 1]
-        grouped = self.dw_group_on and self._side is None
+        grouped = self.dw_group_on
         if grouped:
             self._defer = []
         self._ffn_bwd(bb, pre, bb.d_x2[l], bb.d_h[l], bb.d_s3[l], st[4:6], "norm3", sd("drop3"), bf,

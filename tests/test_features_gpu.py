@@ -35,12 +35,14 @@ def test_autocorr_matches_reference_fixture(golden):
 
 
 @pytest.mark.parametrize("L,hop,n_lags", [(1470, 735, 187), (800, 400, 187), (1470, 735, 191), (266, 133, 40),
-                                           (64, 32, 10), (1801, 900, 150)])
+                                           (64, 32, 10), (1801, 900, 150), (2048, 1024, 187)])
 def test_autocorr_kernel_matches_oracle_across_frame_lengths(L, hop, n_lags):
     """nstl_autocorr (the f64 MFMA kernel: 64-sample k-steps, 13 column tiles,
     tiles past the frame skipped) at other sample rates' frame lengths, lag
     counts up to its 191 limit, frames shorter than one k-step, and a frame
-    length that is not a multiple of 16, against the oracle's direct products.
+    length that is not a multiple of 16, against the oracle's direct products;
+    a 2048-sample frame is past that kernel's LDS budget and takes the
+    register-tiled VALU kernel (frame lengths 1857..4096).
     The frame mean is the exact f32-rounded mean on the GPU and numpy's f32
     pairwise sum in the reference; at 64-sample frames that DC difference alone
     moves the normalised lags by up to ~2e-6 (5e-5 relative), so that case is held
@@ -168,8 +170,11 @@ def test_cmvn_and_pair_reduce_match_reference_fixtures(golden, key):
         np.testing.assert_allclose(got[:, o * C:(o + 1) * C], want, rtol=1e-4, atol=1e-5)
 
 
-@pytest.mark.parametrize("seconds,seed,silent", [(0.6, 11, False), (0.35, 12, True)])
-def test_fused_stft_mel_matches_f64(seconds, seed, silent):
+@pytest.mark.parametrize("seconds,seed,silent,sr,n_fft,hop", [
+    pytest.param(0.6, 11, False, 88200, 1470, 735, id="0.6-11-False"),
+    pytest.param(0.35, 12, True, 88200, 1470, 735, id="0.35-12-True"),
+    pytest.param(0.6, 11, False, 96000, 1600, 800, id="0.6-11-False-96000")])
+def test_fused_stft_mel_matches_f64(seconds, seed, silent, sr, n_fft, hop):
     """nstl_stft_mel (mixed-radix f32 FFT in LDS, |X|^2, Slaney bands) against the
     f64 numpy STFT power times the f64 mel basis (oracle/data_ref.mfcc_120's
     first steps).  Tolerance per frame: 2e-6 of the largest band of the frame and
@@ -177,9 +182,9 @@ def test_fused_stft_mel_matches_f64(seconds, seed, silent):
     transform as its real and imaginary parts, so each carries f32 rounding of the
     pair's energy: a silent frame beside a loud one reads ~1e-7 of it, far under
     the dB floor, top_db 80, of the MFCC that follows) plus 2e-5 relative (f32 FFT
-    rounding ~ log2(n) eps)."""
+    rounding ~ log2(n) eps).  n_fft = 1600 (96 kHz) is past the wave-per-pair
+    kernel's 1536 and takes the workgroup-per-8-frames kernel."""
     from neurosync_trainer_lite_amd import _hip as K
-    sr, n_fft, hop = 88200, 1470, 735
     y = synth_audio(seconds, seed)
     if silent:  # a silent lead-in: bands near zero in the first frames
         y[:4000] = 0

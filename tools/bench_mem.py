@@ -74,7 +74,7 @@ def ln_bwd(n_part, part, n_masks=2):
     K.ln_bwd(a)
 
 
-parts = [int(v) for v in sys.argv[1:]] or [int(os.environ.get("NSTL_LN_PARTS", "256"))]
+parts = [int(v) for v in sys.argv[1:]] or [256]
 for nm in (1, 2, 0):
     line("LayerNorm fwd (%d masks)" % nm, t(lambda: ln_fwd(nm)), R * D * 2 * 4)
 for n_part in parts:
