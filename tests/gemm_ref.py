@@ -8,6 +8,7 @@ Tensors may live on any device: the f64 products run where the operands are."""
 import numpy as np
 import torch
 
+from tests import fp8_table_ref as F8
 from tests import rowwise_ref as R
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU_DROP, EPI_BIAS_ROPE, EPI_DRELU_DROP = 0, 1, 2, 3, 4
@@ -16,6 +17,22 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_RELU_DROP, EPI_BIAS_ROPE, EPI_DRELU_DROP = 0, 1, 2,
 # magnitude its roundings act on (tests/test_tight_parity_gpu.py, K up to 16,384).
 E32 = 1e-5
 BF16_HALF_ULP = 2.0 ** -8  # one rounding to bf16: at most 2^-8 |v|
+# fp8 operands: products of two e4m3 values are exact in f32; what is left is how the
+# scaled f8f6f4 MFMA adds its 64 or 128 products, and the f32 chain over the K blocks.
+# The project's bound E32 is kept wherever the kernels meet it.  They do not at K = 64
+# and K = 128 with f32 C (the ring kernel, 1.90 and 1.31 of E32 mag), and neither does
+# the instruction alone: tools/fp8_mfma_accum_probe.py (one wave, one chained
+# v_mfma_scale_f32_32x32x64_f8f6f4 on register operands, no staging, no epilogue, against
+# f64; profiles/fp8_mfma_accum.txt) shows a worst err / mag of 2.299e-5 at K = 64 and
+# 1.417e-5 at K = 128 on row-quantised codes.  E8 at those K is twice the probe's
+# figure; a kernel that exceeds E8 mag is a finding.  It comes from the probe, not from
+# a GEMM kernel's output.
+E8_PROBED = {64: 2 * 2.299e-5, 128: 2 * 1.417e-5}
+
+
+def e8(K):
+    """Per-element bound of the fp8 accumulation over K, relative to mag."""
+    return E8_PROBED.get(K, E32)
 
 
 def f32v(x):
@@ -56,7 +73,11 @@ def keep_flat(seed, M, N, p):
 
 def operand(X, rows, red, kmajor):
     """The [rows][red] f64 matrix of a stored operand: X is [rows][ld] when K-major,
-    [red][ld] otherwise (padding columns are cut off)."""
+    [red][ld] otherwise (padding columns are cut off).  float8_e4m3fn operands are
+    decoded from their code bytes by fp8_table_ref's table, not by torch's cast."""
+    if X.dtype == torch.float8_e4m3fn:
+        table = torch.from_numpy(F8.CODE_VALUES).to(X.device)
+        X = table[X.detach().view(torch.uint8).long()]
     X = X.detach().double()
     return X[:rows, :red] if kmajor else X[:red, :rows].T
 
@@ -78,11 +99,13 @@ def rope_mag(mag, cos, sin, T, rope_dim):
 
 
 def gemm_ref(A, B, M, N, K, *, a_kmajor=True, b_kmajor=True, alpha=1.0, beta=0.0, C0=None, epilogue=EPI_NONE,
-             bias=None, aux=None, p_drop=0.0, seed=0, rope=None, rope_cols=0):
+             bias=None, aux=None, p_drop=0.0, seed=0, rope=None, rope_cols=0, a_scale=None, b_scale=None):
     """(ref, mag), f64 [M][N], of one call described by the K.gemm keywords.
 
-    acc = A(i, :) . B(j, :) of the operands as stored (bf16 values are exact in f64);
-    v = alpha acc; + bias[j] (every epilogue but NONE and DRELU_DROP); then
+    acc = A(i, :) . B(j, :) of the operands as stored (bf16 values and decoded e4m3
+    code bytes are exact in f64); v = alpha acc, for fp8 operands v = alpha a_scale[i]
+    b_scale[j] acc with the f32 row scales of A [M] and B [N] (mag carries the same
+    factors on |qa| @ |qb|); + bias[j] (every epilogue but NONE and DRELU_DROP); then
       BIAS_RELU_DROP: max(v, 0) keep(i, j) / (1 - p)  (keep_flat)
       BIAS_ROPE:      columns < rope_cols rotated (rowwise_ref.rope_ref; rope =
                       (cos, sin, rope_T, rope_dim))
@@ -100,6 +123,9 @@ def gemm_ref(A, B, M, N, K, *, a_kmajor=True, b_kmajor=True, alpha=1.0, beta=0.0
     alpha, beta = f32v(alpha), f32v(beta)
     v = alpha * (A64 @ B64.T)
     mag = abs(alpha) * (A64.abs() @ B64.abs().T)
+    if a_scale is not None or b_scale is not None:
+        sc = a_scale.detach().double().to(dev)[:M, None] * b_scale.detach().double().to(dev)[None, :N]
+        v, mag = v * sc, mag * sc.abs()
     if bias is not None and epilogue not in (EPI_NONE, EPI_DRELU_DROP):
         b = bias.detach().double().to(dev)[:N]
         v = v + b
@@ -128,10 +154,10 @@ def gemm_ref(A, B, M, N, K, *, a_kmajor=True, b_kmajor=True, alpha=1.0, beta=0.0
     return v, mag
 
 
-def bound(ref, mag, c_dtype):
+def bound(ref, mag, c_dtype, e=E32):
     """Per-element bound of a stored output: E32 mag for f32; for bf16 the store's
     rounding on top, 2^-8 |ref| + (1 + 2^-8) E32 mag (the rounding acts on the f32
-    value, which is within E32 mag of ref)."""
+    value, which is within E32 mag of ref).  fp8 operands: e = e8(K) in place of E32."""
     if c_dtype == torch.float32:
-        return E32 * mag
-    return BF16_HALF_ULP * ref.abs() + (1.0 + BF16_HALF_ULP) * E32 * mag
+        return e * mag
+    return BF16_HALF_ULP * ref.abs() + (1.0 + BF16_HALF_ULP) * e * mag

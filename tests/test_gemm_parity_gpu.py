@@ -2,7 +2,7 @@
 MI355X against tests/gemm_ref.py (itself proven in tests/test_gemm_ref.py): the
 128x128 kernel, the 8-wave 256x256 ring kernel, the 4-wave persistent gemm4 kernel,
 split-K with splitk_reduce and the grouped launches, at the tile, K and stride edges
-where each changes path.  fp8 operands are out of scope here (tests/test_fp8_gpu.py).
+where each changes path.  fp8 operands: tests/test_fp8_parity_gpu.py, by the same reference.
 
 Every case
   - gives C as an [M + 2][ldc] NaN-filled buffer (the live M x N window set to C0

@@ -126,3 +126,29 @@ def test_bound_formulas():
     got = x.float().bfloat16().double()
     assert ((got - x).abs() <= G.bound(x, x.abs(), torch.bfloat16)).all()
     assert ((got + 2.0 ** -7 - x).abs() > G.bound(x, x.abs(), torch.bfloat16)).all()
+
+
+def test_fp8_call_matches_oracle_fp8_gemm():
+    """a_scale / b_scale with e4m3 operands: oracle.fp8_ref.gemm of the same codes
+    (padded rows holding 0x7F, the e4m3 NaN, past K; scales followed by NaN), alpha,
+    and the bias epilogue on top; mag carries the scales on |qa| @ |qb|."""
+    from oracle import fp8_ref
+    M, N, Kd = 37, 24, 128
+    qa, sa = fp8_ref.quant_rows(rnd(M, Kd, seed=70).float())
+    qb, sb = fp8_ref.quant_rows(rnd(N, Kd, seed=71, scale=0.05).float())
+    A = torch.full((M, Kd + 16), 0x7F, dtype=torch.uint8).view(torch.float8_e4m3fn)
+    B = torch.full((N, Kd + 32), 0x7F, dtype=torch.uint8).view(torch.float8_e4m3fn)
+    A.view(torch.uint8)[:, :Kd] = qa.view(torch.uint8)
+    B.view(torch.uint8)[:, :Kd] = qb.view(torch.uint8)
+    sa_p, sb_p = torch.cat([sa, torch.tensor([float("nan")])]), torch.cat([sb, torch.tensor([float("nan")])])
+    want = fp8_ref.gemm(qa, sa, qb, sb)
+    ref, mag = G.gemm_ref(A, B, M, N, Kd, a_scale=sa_p, b_scale=sb_p)
+    assert torch.allclose(ref, want, rtol=1e-14, atol=0)
+    want_mag = (qa.double().abs() @ qb.double().abs().T) * sa.double()[:, None] * sb.double()[None, :]
+    assert torch.allclose(mag, want_mag, rtol=1e-14, atol=0) and (mag >= ref.abs()).all()
+    bias = rnd(N, seed=72).float()
+    ref, mag = G.gemm_ref(A, B, M, N, Kd, a_scale=sa_p, b_scale=sb_p, alpha=0.75, epilogue=G.EPI_BIAS, bias=bias)
+    assert ((ref - (0.75 * want + bias.double())).abs() <= 1e-14 * mag).all()
+    assert torch.allclose(mag, 0.75 * want_mag + bias.double().abs(), rtol=1e-14, atol=0)
+    assert G.e8(192) == G.e8(1024) == G.E32 and G.e8(64) == 2 * 2.299e-5 and G.e8(128) == 2 * 1.417e-5
+    assert torch.equal(G.bound(ref, mag, torch.float32, G.e8(64)), G.e8(64) * mag)
