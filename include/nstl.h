@@ -327,7 +327,8 @@ int nstl_autocorr(const float* y, int64_t n_samples, int frame_length, int hop_l
  * centre-padded periodic-Hann frames of n_fft = int(0.01667 sr) every n_fft/2
  * samples, mixed-radix FFT (n_fft over radices 2, 3, 4, 5, 7), |X|^2 of bins
  * 0..n_fft/2, 128 Slaney mel filters.  mel_out: f32 [n_frames][128] power,
- * n_frames = 1 + n_samples / (n_fft/2).  nstl_features runs the same kernel. */
+ * n_frames = 1 + (n_samples + 2 (n_fft/2) - n_fft) / (n_fft/2), which is
+ * 1 + n_samples / (n_fft/2) for an even n_fft.  nstl_features runs the same kernel. */
 int nstl_stft_mel(const float* y, int64_t n_samples, int sr, float* mel_out, int n_frames, void* stream);
 
 /* Combined per-clip audio features: extract_and_combine_features after the

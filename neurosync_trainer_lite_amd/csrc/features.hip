@@ -975,7 +975,9 @@ __global__ __launch_bounds__(256) void cmvn_delta_out_kernel(const float* __rest
     Q += part[(c * CMVN_CH + k) * 2 + 1];
   }
   const float mean = (float)(S / (double)F);
-  const double dev = Q - 2.0 * (double)mean * S + (double)F * (double)mean * (double)mean;
+  // a sum of squares; the expanded form's rounding (a few ulps of Q) can leave it below
+  // zero on a constant row, and sqrtf of that is NaN
+  const double dev = fmax(Q - 2.0 * (double)mean * S + (double)F * (double)mean * (double)mean, 0.0);
   const float sd = sqrtf((float)dev / (float)F);
   const float inv = 1.f / (sd + 1e-10f);
   const float* x = mfcc + (int64_t)c * F;
@@ -1038,7 +1040,10 @@ FeatLayout feat_layout(int64_t n_samples, int sr) {
   L.hop = L.n_fft / 2;
   L.nb = L.n_fft / 2 + 1;
   L.kp = (L.n_fft + 3) / 4 * 4;
-  L.F = L.hop > 0 ? (int)(1 + n_samples / L.hop) : 0;
+  // librosa's centred frame count, 1 + (n + 2 (n_fft / 2) - n_fft) / hop: what nstl_autocorr
+  // expects as well.  1 + n / hop for an even n_fft; an odd n_fft (44.1 kHz: 735) has one
+  // frame fewer when n is a whole number of hops
+  L.F = L.hop > 0 ? (int)((n_samples + 2 * (L.n_fft / 2) - L.n_fft) / L.hop + 1) : 0;
   L.F60 = (L.F + 1) / 2;
   size_t off = 0;
   L.frames = off; off += align256((size_t)L.F * L.kp * 4);

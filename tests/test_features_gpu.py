@@ -168,6 +168,11 @@ def test_cmvn_and_pair_reduce_match_reference_fixtures(golden, key):
     for o in (1, 2):
         want = data_ref.reduce_features(data_ref.savgol_delta(cm, o)).T
         np.testing.assert_allclose(got[:, o * C:(o + 1) * C], want, rtol=1e-4, atol=1e-5)
+    # and under the bound counted from the kernel's roundings (tests/features_ref.py),
+    # from the f32 rows the kernel was given
+    from tests import features_ref
+    ref, bound = features_ref.cmvn_ref(x.astype(np.float32))
+    assert bound.max() < 1e-5 and np.all(np.abs(got - ref) <= bound), np.max(np.abs(got - ref) / bound)
 
 
 @pytest.mark.parametrize("seconds,seed,silent,sr,n_fft,hop", [
@@ -203,5 +208,10 @@ def test_fused_stft_mel_matches_f64(seconds, seed, silent, sr, n_fft, hop):
     pair = np.maximum(fmax, fmax[np.minimum(np.arange(F) ^ 1, F - 1)])
     bound = 2e-6 * pair[:, None] + 2e-5 * np.abs(ref)
     assert np.all(np.abs(got - ref) <= bound + 1e-30), np.max(np.abs(got - ref) / (bound + 1e-30))
+    # and under the smaller of that bound and the per-band one counted from the FFT's
+    # roundings (tests/features_ref.py)
+    from tests import features_ref
+    ref2, bound2 = features_ref.mel_stage(y, sr)
+    assert np.all(bound2 <= bound) and np.all(np.abs(got - ref2) <= bound2), np.max(np.abs(got - ref2) / bound2)
     with pytest.raises(RuntimeError, match="n_frames"):
         K.stft_mel(yd, len(y), sr, mel, F + 1)
