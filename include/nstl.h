@@ -77,15 +77,24 @@ typedef struct nstl_gemm_args {
                                           (utils/training_utils.py:73) without re-reading them */
 } nstl_gemm_args;
 int nstl_gemm(const nstl_gemm_args* args, void* stream);
-/* Rows of colsum_part for these arguments, or 0 when the call cannot produce it. */
+/* The two size queries answer for the 8-wave 256x256 ring kernels, which take
+   the call whenever the 4-wave kernel does not (same buffer layouts in both), so
+   the answer holds whichever of them runs.  Both need bf16 C, beta 0 and no
+   split-K; bf16 operands also K % 64 == 0, M, N >= 256 and at least 32 tiles
+   ceil(M/256) x ceil(N/256) (below that the 128x128 kernel may run, which has no
+   side outputs: 0, even for whole-tile shapes the 4-wave kernel would take); fp8
+   operands any M, N.  0 for arguments nstl_gemm rejects.
+   Rows of colsum_part, ceil(M/128), with the DRELU_DROP epilogue; else 0. */
 int nstl_gemm_colsum_rows(const nstl_gemm_args* args);
-/* 64-bit words of relu_mask for these arguments (the 256 kernel's ReLU-dropout or
-   dReLU epilogue, bf16), or 0 when the call cannot use it. */
+/* 64-bit words of relu_mask, ceil(M/64) * 8 * ceil(N/8), with the DRELU_DROP
+   epilogue or BIAS_RELU_DROP and even N; else 0. */
 int64_t nstl_gemm_relu_mask_words(const nstl_gemm_args* args);
 
 /* Up to NSTL_GEMM_GROUP_MAX independent problems in ONE launch (grouped GEMM):
-   each a bf16 problem for the 256x256 kernel (M, N >= 256, K % 64 == 0), no
-   epilogue, no split-K, all with the same a_kmajor / b_kmajor / c_dtype and
+   each a bf16 problem for the 256x256 kernel (M, N >= 256, K % 64 == 0), all
+   with no epilogue or all with NSTL_EPI_BIAS_ROPE on one shared table (the same
+   rope_cos, rope_sin, rope_T, rope_dim; bias and rope_cols per problem), no
+   split-K, all with the same a_kmajor / b_kmajor / c_dtype and
    beta use (0 / nonzero); alpha, beta, pointers and shapes per problem.  The
    weight gradients of one decoder layer (utils/model.py:193-216 Linears,
    backward) are 256 tiles: one full round with no split-K partials; those of
@@ -371,8 +380,8 @@ enum {
   NSTL_K_GEMM128 = 0,        /* 128x128 GEMM launches (small / f32 problems) */
   NSTL_K_GEMM_RING,          /* 256x256 LDS-DMA ring GEMM launches */
   NSTL_K_GEMM_RING_TILES,    /*   ... their 256x256 output tiles */
-  NSTL_K_GEMM_GROUP,         /* grouped ring GEMM launches (weight gradients) */
-  NSTL_K_GEMM_GROUP_TILES,   /*   ... their tiles */
+  NSTL_K_GEMM_GROUP,         /* the grouped ring kernel is gone: stays 0 (slot kept for the bindings' order) */
+  NSTL_K_GEMM_GROUP_TILES,   /*   ... stays 0 (a group counts as NSTL_K_GEMM4, or one NSTL_K_GEMM_RING per problem) */
   NSTL_K_GEMM_SPLITK_REDUCE, /* split-K combine launches */
   NSTL_K_GEMM_FP8,           /* fp8 GEMM launches (either kernel) */
   NSTL_K_ATTN_FWD,           /* MFMA attention forward */

@@ -22,6 +22,7 @@
 #include <string>
 
 #include "common.h"
+#include "gemm_host.h"
 #include "status.h"
 
 namespace {
@@ -1109,19 +1110,6 @@ int ring_epi_mode(const nstl_gemm_args* a, const GemmParams& p) {
   return EM_GENERIC;
 }
 
-template <bool AK, bool BKM>
-void launch_ring_em(int em, dim3 grid, dim3 block, hipStream_t st, const GemmParams& p) {
-  switch (em) {
-    case EM_BF16: hipLaunchKernelGGL((gemm256r_kernel<AK, BKM, EM_BF16>), grid, block, 0, st, p); break;
-    case EM_RELU_DROP: hipLaunchKernelGGL((gemm256r_kernel<AK, BKM, EM_RELU_DROP>), grid, block, 0, st, p); break;
-    case EM_ROPE: hipLaunchKernelGGL((gemm256r_kernel<AK, BKM, EM_ROPE>), grid, block, 0, st, p); break;
-    case EM_DRELU: hipLaunchKernelGGL((gemm256r_kernel<AK, BKM, EM_DRELU>), grid, block, 0, st, p); break;
-    case EM_F32: hipLaunchKernelGGL((gemm256r_kernel<AK, BKM, EM_F32>), grid, block, 0, st, p); break;
-    case EM_WS: hipLaunchKernelGGL((gemm256r_kernel<AK, BKM, EM_WS>), grid, block, 0, st, p); break;
-    default: hipLaunchKernelGGL((gemm256r_kernel<AK, BKM, EM_GENERIC>), grid, block, 0, st, p); break;
-  }
-}
-
 // split-K combine: C = sum_z ws[z] (+bias) (+beta*C)
 __global__ void splitk_reduce(const float* ws, int splits, int M, int N, char* C, int64_t ldc, int c_f32,
                               float beta, const float* bias) {
@@ -1145,14 +1133,25 @@ __global__ void splitk_reduce(const float* ws, int splits, int M, int N, char* C
   }
 }
 
-int launch_big(const nstl_gemm_args* a, GemmParams& p, int splits, hipStream_t st) {
+// the 8-wave ring kernel with epilogue mode `em`: gemm256r_kernel (bf16, any layout) or gemm256f8_kernel
+int launch_ring(const nstl_gemm_args* a, const GemmParams& p, int em, int splits, hipStream_t st) {
   const int nt = ((a->M + BIG - 1) / BIG) * ((a->N + BIG - 1) / BIG);
-  dim3 grid(nt, splits), block(BIG_NT);
-  const int em = ring_epi_mode(a, p);
-  if (a->a_kmajor && a->b_kmajor) launch_ring_em<true, true>(em, grid, block, st, p);
-  else if (a->a_kmajor && !a->b_kmajor) launch_ring_em<true, false>(em, grid, block, st, p);
-  else if (!a->a_kmajor && !a->b_kmajor) launch_ring_em<false, false>(em, grid, block, st, p);
-  else launch_ring_em<false, true>(em, grid, block, st, p);
+  const dim3 grid(nt, splits), block(BIG_NT);
+  if (a->dtype == NSTL_FP8) {
+    nstl::with_em<EM_BF16, EM_RELU_DROP, EM_ROPE, EM_DRELU, EM_F32>(em, [&](auto EM) {
+      hipLaunchKernelGGL((gemm256f8_kernel<decltype(EM)::value>), grid, block, 0, st, p);
+    });
+    NSTL_LAUNCH_CHECK("nstl_gemm (FP8)");
+    nstl::count(NSTL_K_GEMM_FP8);
+    if (em == EM_ROPE) nstl::count(NSTL_K_GEMM_FP8_ROPE);
+    return 0;
+  }
+  nstl::with_layout(a->a_kmajor, a->b_kmajor, [&](auto AK, auto BKM) {
+    nstl::with_em<EM_GENERIC, EM_BF16, EM_RELU_DROP, EM_ROPE, EM_DRELU, EM_F32, EM_WS>(em, [&](auto EM) {
+      hipLaunchKernelGGL((gemm256r_kernel<decltype(AK)::value, decltype(BKM)::value, decltype(EM)::value>), grid, block,
+                         0, st, p);
+    });
+  });
   NSTL_LAUNCH_CHECK("nstl_gemm (256 ring)");
   nstl::count(NSTL_K_GEMM_RING);
   nstl::count(NSTL_K_GEMM_RING_TILES, (long long)nt * splits);
@@ -1160,17 +1159,12 @@ int launch_big(const nstl_gemm_args* a, GemmParams& p, int splits, hipStream_t s
 }
 
 template <typename T>
-int launch_typed(const nstl_gemm_args* a, GemmParams& p, int splits, hipStream_t st) {
+int launch_128(const nstl_gemm_args* a, const GemmParams& p, int splits, hipStream_t st) {
   const int nt = ((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN);
-  dim3 grid(nt, splits), block(NTHREADS);
-  if (a->a_kmajor && a->b_kmajor)
-    hipLaunchKernelGGL((gemm_kernel<T, true, true>), grid, block, 0, st, p);
-  else if (a->a_kmajor && !a->b_kmajor)
-    hipLaunchKernelGGL((gemm_kernel<T, true, false>), grid, block, 0, st, p);
-  else if (!a->a_kmajor && !a->b_kmajor)
-    hipLaunchKernelGGL((gemm_kernel<T, false, false>), grid, block, 0, st, p);
-  else
-    hipLaunchKernelGGL((gemm_kernel<T, false, true>), grid, block, 0, st, p);
+  const dim3 grid(nt, splits), block(NTHREADS);
+  nstl::with_layout(a->a_kmajor, a->b_kmajor, [&](auto AK, auto BKM) {
+    hipLaunchKernelGGL((gemm_kernel<T, decltype(AK)::value, decltype(BKM)::value>), grid, block, 0, st, p);
+  });
   NSTL_LAUNCH_CHECK("nstl_gemm");
   nstl::count(NSTL_K_GEMM128);
   return 0;
@@ -1240,117 +1234,221 @@ int make_params(const nstl_gemm_args* a, GemmParams& p) {
   return 0;
 }
 
-}  // namespace
-namespace nstl {
-int gemm4_f8(const nstl_gemm_args* a, hipStream_t st, int* handled);  // gemm4.hip
-}
-namespace {
+// ---------------------------------------------------------------------------
+// Routing: which kernel family takes a call, and everything its launch needs.
+// route() / route_grouped() are the only places that evaluate eligibility.
 
-// FP8 operands: the 4-wave kernel for full tiles (gemm4f8_kernel), the fp8 ring
-// kernel otherwise (K-major A and B, K % 64 == 0, no split-K)
-int gemm_f8(const nstl_gemm_args* a, GemmParams& p, hipStream_t st) {
-  NSTL_CHECK_ARG(a->a_kmajor && a->b_kmajor, "nstl_gemm: FP8 needs K-major A and B (Y = X W^T)");
-  NSTL_CHECK_ARG(a->K % 64 == 0, "nstl_gemm: FP8 needs K %% 64 == 0 (got %d)", a->K);
-  NSTL_CHECK_ARG(a->a_scale && a->b_scale, "nstl_gemm: FP8 needs the row scales a_scale [M] and b_scale [N]");
-  NSTL_CHECK_ARG(a->split_k <= 1, "nstl_gemm: FP8: no split-K");
-  {
-    int handled = 0;
-    if (int rc = nstl::gemm4_f8(a, st, &handled)) return rc;
-    if (handled) return 0;
-  }
-  const int em = ring_epi_mode(a, p);
-  NSTL_CHECK_ARG(em == EM_BF16 || em == EM_RELU_DROP || em == EM_ROPE || em == EM_DRELU || em == EM_F32,
-                 "nstl_gemm: FP8 supports the NONE / BIAS / BIAS_RELU_DROP / BIAS_ROPE / DRELU_DROP epilogues "
-                 "(bf16 out without beta, or f32 out without epilogue)");
-  NSTL_CHECK_ARG(!a->relu_mask || em == EM_RELU_DROP || em == EM_DRELU,
-                 "nstl_gemm: relu_mask needs the ReLU-dropout / dReLU epilogue");
-  NSTL_CHECK_ARG(!a->colsum_part || em == EM_DRELU, "nstl_gemm: FP8: colsum_part needs the dReLU epilogue");
-  const int nt = ((a->M + BIG - 1) / BIG) * ((a->N + BIG - 1) / BIG);
-  dim3 grid(nt), block(BIG_NT);
-  switch (em) {
-    case EM_BF16: hipLaunchKernelGGL((gemm256f8_kernel<EM_BF16>), grid, block, 0, st, p); break;
-    case EM_RELU_DROP: hipLaunchKernelGGL((gemm256f8_kernel<EM_RELU_DROP>), grid, block, 0, st, p); break;
-    case EM_ROPE: hipLaunchKernelGGL((gemm256f8_kernel<EM_ROPE>), grid, block, 0, st, p); break;
-    case EM_DRELU: hipLaunchKernelGGL((gemm256f8_kernel<EM_DRELU>), grid, block, 0, st, p); break;
-    default: hipLaunchKernelGGL((gemm256f8_kernel<EM_F32>), grid, block, 0, st, p); break;
-  }
-  NSTL_LAUNCH_CHECK("nstl_gemm (FP8)");
-  nstl::count(NSTL_K_GEMM_FP8);
-  if (em == EM_ROPE) nstl::count(NSTL_K_GEMM_FP8_ROPE);
-  return 0;
+enum { FAM_GEMM4, FAM_RING, FAM_128 };  // gemm4 and the ring each with their fp8 form (dtype NSTL_FP8)
+
+struct Route {
+  int family;
+  int n;                              // problems (1 unless nstl_gemm_grouped)
+  GemmParams p[NSTL_GEMM_GROUP_MAX];  // ring / 128 kernel parameters, split-K chunk and slabs included
+  int em[NSTL_GEMM_GROUP_MAX];        // FAM_RING: each problem's epilogue mode
+  int splits;                         // split-K slabs (grid.y), 1 without
+  nstl::Gemm4Route g4;                // FAM_GEMM4
+  g4::GroupParams gp;
+};
+static_assert(NSTL_GEMM_GROUP_MAX == g4::GROUP_MAX, "one group limit");
+static_assert(EM_BF16 == g4::EM_BF16 && EM_RELU_DROP == g4::EM_RELU_DROP && EM_ROPE == g4::EM_ROPE &&
+                  EM_DRELU == g4::EM_DRELU && EM_F32 == g4::EM_F32,
+              "one epilogue-mode numbering");
+
+// read per call (a getenv per GEMM), so a test can compare both arms in one process
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
 
-bool big_ok(const nstl_gemm_args* a) {
+// What the bf16 and the fp8 form of the 4-wave kernel differ in.
+struct G4Type {
+  int dtype, esz, bk;  // operands, their size, K elements per stage
+  bool f32_out;        // has an EM_F32 instantiation (fp8 with f32 C: the ring kernel, tests only)
+  int rope_esz;        // the RoPE table must fit ROPE_LDS with entries this small: f32; fp8 also
+                       // holds it as bf16 when only that fits (T = 256 with head dim 64)
+  bool kmajor_only;    // fp8: A [M][K] and B [N][K]; bf16: the layouts nstl::g4_has lists
+};
+constexpr G4Type G4_BF16 = {NSTL_BF16, 2, g4::BK, true, 4, false};
+constexpr G4Type G4_F8 = {NSTL_FP8, 1, g4::F8_BK, false, 2, true};
+
+// The one eligibility predicate of the 4-wave kernels: the epilogue mode
+// (g4::EM_*, the ring's numbering) with which the kernel of type `t` takes `a`,
+// and q filled for it; 0 when it does not (partial tiles, split-K, beta != 0,
+// dReLU without keep bits, a RoPE table past the LDS budget, ...).
+int g4_take(const nstl_gemm_args* a, const G4Type& t, g4::Params& q) {
+  if (a->dtype != t.dtype || a->split_k > 1 || a->beta != 0.f) return 0;
+  const bool f32_c = a->c_dtype == NSTL_F32;
+  if (a->sq_part != nullptr && !(t.f32_out && f32_c)) return 0;
+  // side outputs only with the epilogue that produces them (anything else goes on
+  // to the ring kernel's argument checks)
+  if (a->colsum_part != nullptr && a->epilogue != NSTL_EPI_DRELU_DROP) return 0;
+  if (a->relu_mask != nullptr && a->epilogue != NSTL_EPI_BIAS_RELU_DROP && a->epilogue != NSTL_EPI_DRELU_DROP)
+    return 0;
+  int em = 0;
+  switch (a->epilogue) {
+    case NSTL_EPI_NONE: em = !f32_c ? EM_BF16 : t.f32_out ? EM_F32 : 0; break;
+    case NSTL_EPI_BIAS: em = !f32_c ? EM_BF16 : 0; break;
+    case NSTL_EPI_BIAS_RELU_DROP: em = !f32_c && (a->N & 1) == 0 ? EM_RELU_DROP : 0; break;
+    case NSTL_EPI_BIAS_ROPE:
+      em = !f32_c && a->rope_dim % 4 == 0 && a->rope_cols % 16 == 0 &&
+                   (int64_t)a->rope_T * a->rope_dim * t.rope_esz <= g4::ROPE_LDS
+               ? EM_ROPE
+               : 0;
+      break;
+    case NSTL_EPI_DRELU_DROP: em = !f32_c && a->relu_mask != nullptr ? EM_DRELU : 0; break;
+  }
+  if (!em) return 0;
+  if (t.kmajor_only ? !(a->a_kmajor && a->b_kmajor) : !nstl::g4_has(a->a_kmajor, a->b_kmajor, em, false, false, 0))
+    return 0;
+  // K: whole pairs of stages (every tile starts on stage slot 0), at least two pairs
+  if (a->M % g4::TILE || a->N % g4::TILE || a->K % (2 * t.bk) || a->K < 4 * t.bk) return 0;
+  if (((uintptr_t)a->A | (uintptr_t)a->B | (uintptr_t)a->C) % 16) return 0;
+  if (a->lda % (16 / t.esz) || a->ldb % (16 / t.esz) || a->ldc % (f32_c ? 4 : 8)) return 0;
+  // operand extents for the 32-bit buffer offsets; f32 C is stored through a buffer resource too
+  const int64_t ae = (a->a_kmajor ? (int64_t)(a->M - 1) * a->lda + a->K : (int64_t)(a->K - 1) * a->lda + a->M) * t.esz;
+  const int64_t be = (a->b_kmajor ? (int64_t)(a->N - 1) * a->ldb + a->K : (int64_t)(a->K - 1) * a->ldb + a->N) * t.esz;
+  const int64_t ce = f32_c ? (int64_t)a->M * a->ldc * 4 : 0;
+  if (ae >= (1ll << 31) || be >= (1ll << 31) || ce >= (1ll << 31)) return 0;
+
+  memset(&q, 0, sizeof(q));
+  q.A = (const char*)a->A; q.lda = a->lda;
+  q.B = (const char*)a->B; q.ldb = a->ldb;
+  q.C = (char*)a->C; q.ldc = a->ldc;
+  q.M = a->M; q.N = a->N; q.K = a->K;
+  q.alpha = a->alpha;
+  q.bias = a->bias;
+  q.thresh = nstl_drop_thresh(a->p_drop);
+  q.inv_keep = 1.0f / (1.0f - a->p_drop);
+  q.seed = a->seed;
+  q.rope_cos = a->rope_cos; q.rope_sin = a->rope_sin;
+  q.rope_T = a->rope_T; q.rope_dim = a->rope_dim; q.rope_cols = a->rope_cols;
+  q.colsum_part = a->colsum_part;
+  q.relu_mask = a->relu_mask;
+  q.sq_part = a->sq_part;
+  if (t.dtype == NSTL_FP8) {
+    q.a_scale = a->a_scale;
+    q.b_scale = a->b_scale;
+  }
+  q.rope_bf16 = em == EM_ROPE && (int64_t)a->rope_T * a->rope_dim * 4 > g4::ROPE_LDS;
+  q.a_bytes = (uint32_t)ae;
+  q.b_bytes = (uint32_t)be;
+  q.tiles_m = a->M / g4::TILE;
+  q.tiles_n = a->N / g4::TILE;
+  return em;
+}
+
+// Completes a gemm4 decision for the r.gp.n problems g4_take filled with mode
+// `em`; false (the next family takes the call) when the kernel has no such
+// instantiation or the stream's CU mask leaves it no workgroups.
+// R3 (gemm4.h): the stage DMA spread over both half-steps with a 3 + 2 slot
+// ring.  Measured on isolated shapes (profiles/r5_r3_ab.txt, outputs bit-
+// identical): the weight gradients (K = 16,384) 3-6 % faster, K = 4096 shapes
+// ~1 %, the K = 1024 multi-round forward (FFN1) 4-9 % slower, the rest neutral:
+// taken for K >= 2048 (every weight gradient).  NSTL_GEMM4_R3=0: never (A/B).
+bool g4_route(Route& r, const nstl_gemm_args* args, int em, bool f8, bool grouped, hipStream_t st) {
+  const bool ak = args->a_kmajor, bk = args->b_kmajor;
+  if (!em || (!f8 && !nstl::g4_has(ak, bk, em, grouped, false, 0))) return false;
+  const int G = nstl::stream_cus(st);
+  if (G <= 0) return false;
+  int kmin = args->K, tiles = 0;
+  for (int i = 0; i < r.gp.n; ++i) {
+    kmin = std::min(kmin, args[i].K);
+    r.gp.tile_end[i] = tiles += r.gp.g[i].tiles_m * r.gp.g[i].tiles_n;
+  }
+  const bool r3 = !f8 && kmin >= 2048 && env_int("NSTL_GEMM4_R3", 1) && nstl::g4_has(ak, bk, em, grouped, false, 1);
+  r.family = FAM_GEMM4;
+  r.g4 = {em, f8, ak, bk, grouped, r3, !f8 && nstl::g4_has(ak, bk, em, grouped, true, 0), G};
+  return true;
+}
+
+// the 256x256 LDS-DMA ring kernel: bf16, K a multiple of its 64-deep K tile, and at
+// least 32 of its tiles (measured on the 228M step's shapes, tools/bench_gemm.py;
+// smaller/odd problems take the 128 kernel.  A 1024^2 dW split 16 ways on the
+// 256 kernel ties the 128 kernel split 8 ways: 60 vs 61 us, tools/bench_gemm_epi.py)
+bool ring_ok(const nstl_gemm_args* a) {
   const int64_t big_tiles = (int64_t)((a->M + BIG - 1) / BIG) * ((a->N + BIG - 1) / BIG);
   return a->dtype == NSTL_BF16 && a->K % 64 == 0 && a->M >= BIG && a->N >= BIG && big_tiles >= 32;
 }
 
-}  // namespace
-
-namespace nstl {
-int gemm4(const nstl_gemm_args* a, hipStream_t st, int* handled);                   // gemm4.hip
-int gemm4_grouped(const nstl_gemm_args* args, int n, hipStream_t st, int* handled);  // gemm4.hip
-}
-
-extern "C" int nstl_gemm(const nstl_gemm_args* a, void* stream) {
-  GemmParams p;
+// One nstl_gemm call.  Order: the 4-wave kernel when g4_take accepts the call
+// (whole 256^2 tiles, whatever their number) and the stream has CUs for it, else
+// the ring kernel (fp8: always; bf16: ring_ok), else the 128 kernel.
+//
+// st == nullptr is a size query (nstl_gemm_colsum_rows / _relu_mask_words): it
+// has no stream, and its answer sizes a buffer that must be right whichever
+// family the call later reaches (NSTL_GEMM4=0, a stream whose CU mask leaves no
+// workgroups), so it gets the decision without the 4-wave kernel.  Known
+// asymmetry: a whole-tile bf16 problem under 32 tiles runs on gemm4, which
+// would honour keep bits and column sums, but the query answers for the 128
+// kernel, which has neither: 0 (follow-up).
+int route(const nstl_gemm_args* a, const hipStream_t* st, Route& r) {
+  GemmParams& p = r.p[0];
   if (int rc = make_params(a, p)) return rc;
   NSTL_CHECK_ARG(!a->sq_part, "nstl_gemm: sq_part is produced by nstl_gemm_grouped only");
-  if (a->dtype == NSTL_FP8) return gemm_f8(a, p, (hipStream_t)stream);
-  {  // full 256^2 tiles: the 4-wave persistent kernel (gemm4.hip); the rest below
-    int handled = 0;
-    if (int rc = nstl::gemm4(a, (hipStream_t)stream, &handled)) return rc;
-    if (handled) return 0;
+  const bool f8 = a->dtype == NSTL_FP8;
+  if (f8) {
+    NSTL_CHECK_ARG(a->a_kmajor && a->b_kmajor, "nstl_gemm: FP8 needs K-major A and B (Y = X W^T)");
+    NSTL_CHECK_ARG(a->K % 64 == 0, "nstl_gemm: FP8 needs K %% 64 == 0 (got %d)", a->K);
+    NSTL_CHECK_ARG(a->a_scale && a->b_scale, "nstl_gemm: FP8 needs the row scales a_scale [M] and b_scale [N]");
+    NSTL_CHECK_ARG(a->split_k <= 1, "nstl_gemm: FP8: no split-K");
   }
-  const int esz = a->dtype == NSTL_F32 ? 4 : 2;
+  r.n = 1;
+  r.splits = 1;
+  // NSTL_GEMM4=0: no 4-wave kernel at all; NSTL_GEMM4_F8=0: none for fp8 (A/B runs)
+  if (st && a->dtype != NSTL_F32 && env_int("NSTL_GEMM4", 1) && (!f8 || env_int("NSTL_GEMM4_F8", 1))) {
+    memset(&r.gp, 0, sizeof(r.gp));
+    r.gp.n = 1;
+    if (g4_route(r, a, g4_take(a, f8 ? G4_F8 : G4_BF16, r.gp.g[0]), f8, false, *st)) return 0;
+  }
 
-  // the 256x256 LDS-DMA kernel: bf16, K a multiple of its 64-deep K tile, and at
-  // least 32 of its tiles (measured on the 228M step's shapes, tools/bench_gemm.py;
-  // smaller/odd problems take the 128 kernel.  A 1024^2 dW split 16 ways on the
-  // 256 kernel ties the 128 kernel split 8 ways: 60 vs 61 us, tools/bench_gemm_epi.py)
-  const bool big = big_ok(a);
-  NSTL_CHECK_ARG(!a->colsum_part || (big && a->epilogue == NSTL_EPI_DRELU_DROP && a->split_k <= 1 &&
-                                      ring_epi_mode(a, p) == EM_DRELU),
+  int& em = r.em[0];
+  em = ring_epi_mode(a, p);
+  r.family = FAM_RING;
+  if (f8) {
+    NSTL_CHECK_ARG(em == EM_BF16 || em == EM_RELU_DROP || em == EM_ROPE || em == EM_DRELU || em == EM_F32,
+                   "nstl_gemm: FP8 supports the NONE / BIAS / BIAS_RELU_DROP / BIAS_ROPE / DRELU_DROP epilogues "
+                   "(bf16 out without beta, or f32 out without epilogue)");
+    NSTL_CHECK_ARG(!a->relu_mask || em == EM_RELU_DROP || em == EM_DRELU,
+                   "nstl_gemm: relu_mask needs the ReLU-dropout / dReLU epilogue");
+    NSTL_CHECK_ARG(!a->colsum_part || em == EM_DRELU, "nstl_gemm: FP8: colsum_part needs the dReLU epilogue");
+    return 0;
+  }
+  const bool big = ring_ok(a);
+  if (!big) r.family = FAM_128;
+  // the side outputs are the ring kernel's lean epilogues' (bf16 C, beta 0, no split-K)
+  const bool lean = big && a->split_k <= 1;
+  NSTL_CHECK_ARG(!a->colsum_part || (lean && em == EM_DRELU),
                  "nstl_gemm: colsum_part needs the 256 kernel's dReLU epilogue (nstl_gemm_colsum_rows)");
-  NSTL_CHECK_ARG(!a->relu_mask || nstl_gemm_relu_mask_words(a) > 0,
+  NSTL_CHECK_ARG(!a->relu_mask || (lean && (em == EM_RELU_DROP || em == EM_DRELU)),
                  "nstl_gemm: relu_mask needs the 256 kernel's ReLU-dropout / dReLU epilogue (nstl_gemm_relu_mask_words)");
-  const int BKe = big ? 64 : 128 / esz;
-  int splits = a->split_k > 1 ? a->split_k : 1;
-  if (splits > 1) {
+  const int want = a->split_k > 1 ? a->split_k : 1;
+  if (want > 1) {
     NSTL_CHECK_ARG(a->epilogue == NSTL_EPI_NONE || a->epilogue == NSTL_EPI_BIAS,
                    "nstl_gemm: split-K supports NONE/BIAS epilogues only");
-    NSTL_CHECK_ARG(a->workspace != nullptr && a->workspace_bytes >= nstl_gemm_workspace_bytes(a->M, a->N, splits),
+    NSTL_CHECK_ARG(a->workspace != nullptr && a->workspace_bytes >= nstl_gemm_workspace_bytes(a->M, a->N, want),
                    "nstl_gemm: split-K workspace too small");
-    p.ws = (float*)a->workspace;
   }
-  int chunk = (a->K + splits - 1) / splits;
-  chunk = ((chunk + BKe - 1) / BKe) * BKe;
-  splits = (a->K + chunk - 1) / chunk;
-  p.k_chunk = chunk;
-  if (splits == 1) p.ws = nullptr;
-
-  hipStream_t st = (hipStream_t)stream;
-  int rc = big ? launch_big(a, p, splits, st)
-               : a->dtype == NSTL_BF16 ? launch_typed<bf16>(a, p, splits, st) : launch_typed<float>(a, p, splits, st);
-  if (rc) return rc;
-  if (p.ws != nullptr) {
-    const int64_t total = (int64_t)a->M * a->N;
-    int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(splitk_reduce, dim3(blocks), dim3(256), 0, st, p.ws, splits, a->M, a->N, p.C, a->ldc,
-                       p.c_f32, a->beta, a->epilogue == NSTL_EPI_BIAS ? a->bias : nullptr);
-    NSTL_LAUNCH_CHECK("nstl_gemm splitk_reduce");
-    nstl::count(NSTL_K_GEMM_SPLITK_REDUCE);
+  // K chunks of whole K tiles (128 bytes of K; the ring's 64 bf16); fewer slabs when they cover K sooner
+  const int BKe = a->dtype == NSTL_F32 ? 32 : 64;
+  p.k_chunk = ((a->K + want - 1) / want + BKe - 1) / BKe * BKe;
+  r.splits = (a->K + p.k_chunk - 1) / p.k_chunk;
+  if (r.splits > 1) {
+    p.ws = (float*)a->workspace;
+    em = EM_WS;
   }
   return 0;
 }
 
-extern "C" int nstl_gemm_grouped(const nstl_gemm_args* args, int n, void* stream) {
+// One nstl_gemm_grouped call: one gemm4 launch when every problem is eligible
+// with the same mode, else (partial tiles, beta != 0, K % 128 != 0, NSTL_GEMM4=0)
+// one ring launch per problem, in order, whatever its tile count (the ring
+// epilogue writes sq_part, one slot per (tile, wave)).
+int route_grouped(const nstl_gemm_args* args, int n, hipStream_t st, Route& r) {
   NSTL_CHECK_ARG(args != nullptr && n >= 1 && n <= NSTL_GEMM_GROUP_MAX, "nstl_gemm_grouped: 1..%d problems (got %d)",
                  NSTL_GEMM_GROUP_MAX, n);
   for (int g = 0; g < n; ++g) {
     const nstl_gemm_args* a = args + g;
-    GemmParams p;
-    if (int rc = make_params(a, p)) return rc;
+    if (int rc = make_params(a, r.p[g])) return rc;
     NSTL_CHECK_ARG(a->dtype == NSTL_BF16 && a->K % 64 == 0 && a->M >= BIG && a->N >= BIG,
                    "nstl_gemm_grouped: problem %d is not a 256-kernel problem (bf16, M, N >= 256, K %% 64 == 0)", g);
     // no epilogue (the weight gradients), or bias + RoPE with one shared table
@@ -1365,49 +1463,71 @@ extern "C" int nstl_gemm_grouped(const nstl_gemm_args* args, int n, void* stream
                        (a->rope_cos == args[0].rope_cos && a->rope_sin == args[0].rope_sin &&
                         a->rope_T == args[0].rope_T && a->rope_dim == args[0].rope_dim),
                    "nstl_gemm_grouped: problem %d: RoPE problems share one table (cos, sin, T, dim)", g);
-    const int em = ring_epi_mode(a, p);
+    const int em = r.em[g] = ring_epi_mode(a, r.p[g]);
     NSTL_CHECK_ARG(em == EM_F32 || em == EM_BF16 || (em == EM_ROPE && a->epilogue == NSTL_EPI_BIAS_ROPE),
                    "nstl_gemm_grouped: f32 output, or bf16 without beta");
     NSTL_CHECK_ARG(!a->sq_part || em == EM_F32, "nstl_gemm_grouped: sq_part needs f32 output");
   }
-  hipStream_t st = (hipStream_t)stream;
-  {  // full tiles, beta 0: one launch of the 4-wave persistent kernel (gemm4.hip)
-    int handled = 0;
-    if (int rc = nstl::gemm4_grouped(args, n, st, &handled)) return rc;
-    if (handled) return 0;
+  r.n = n;
+  r.splits = 1;
+  if (env_int("NSTL_GEMM4", 1)) {
+    memset(&r.gp, 0, sizeof(r.gp));
+    r.gp.n = n;
+    int em = g4_take(args, G4_BF16, r.gp.g[0]);
+    for (int g = 1; g < n && em; ++g)
+      if (g4_take(args + g, G4_BF16, r.gp.g[g]) != em) em = 0;
+    if (g4_route(r, args, em, false, true, st)) return 0;
   }
-  // anything else (partial tiles, beta != 0, K % 128 != 0, NSTL_GEMM4=0): one
-  // 8-wave ring launch per problem, in order, whatever its tile count (the ring
-  // epilogue writes sq_part, one slot per (tile, wave), as the grouped kernel did)
-  for (int g = 0; g < n; ++g) {
-    GemmParams p;
-    if (int rc = make_params(args + g, p)) return rc;
-    if (int rc = launch_big(args + g, p, 1, st)) return rc;
+  r.family = FAM_RING;
+  return 0;
+}
+
+int launch(const nstl_gemm_args* args, Route& r, hipStream_t st) {
+  if (r.family == FAM_GEMM4) return nstl::gemm4_launch(r.gp, r.g4, st);
+  for (int g = 0; g < r.n; ++g) {
+    const nstl_gemm_args* a = args + g;
+    if (int rc = r.family == FAM_RING         ? launch_ring(a, r.p[g], r.em[g], r.splits, st)
+                 : a->dtype == NSTL_BF16 ? launch_128<bf16>(a, r.p[g], r.splits, st)
+                                         : launch_128<float>(a, r.p[g], r.splits, st))
+      return rc;
+  }
+  const GemmParams& p = r.p[0];
+  if (p.ws != nullptr) {  // split-K (one problem)
+    const int64_t total = (int64_t)p.M * p.N;
+    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(splitk_reduce, dim3(blocks), dim3(256), 0, st, p.ws, r.splits, p.M, p.N, p.C, p.ldc, p.c_f32,
+                       p.beta, p.epi == NSTL_EPI_BIAS ? p.bias : nullptr);
+    NSTL_LAUNCH_CHECK("nstl_gemm splitk_reduce");
+    nstl::count(NSTL_K_GEMM_SPLITK_REDUCE);
   }
   return 0;
 }
 
+}  // namespace
+
+extern "C" int nstl_gemm(const nstl_gemm_args* a, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  Route r;
+  if (int rc = route(a, &st, r)) return rc;
+  return launch(a, r, st);
+}
+
+extern "C" int nstl_gemm_grouped(const nstl_gemm_args* args, int n, void* stream) {
+  Route r;
+  if (int rc = route_grouped(args, n, (hipStream_t)stream, r)) return rc;
+  return launch(args, r, (hipStream_t)stream);
+}
+
+// The size queries: 0 for a call nstl_gemm rejects, and for one whose family
+// (see route) has no such side output.  Both ring kernels share the layouts.
 extern "C" int nstl_gemm_colsum_rows(const nstl_gemm_args* a) {
-  GemmParams p;
-  if (a == nullptr || make_params(a, p) != 0) return 0;
-  if (a->dtype == NSTL_FP8)  // the fp8 ring kernel's dReLU epilogue (same 128-row partial layout)
-    return a->epilogue == NSTL_EPI_DRELU_DROP && a->split_k <= 1 && a->c_dtype == NSTL_BF16 &&
-                   ring_epi_mode(a, p) == EM_DRELU ? (a->M + 127) / 128 : 0;
-  if (!big_ok(a) || a->epilogue != NSTL_EPI_DRELU_DROP || a->split_k > 1) return 0;
-  if (ring_epi_mode(a, p) != EM_DRELU) return 0;
+  Route r;
+  if (route(a, nullptr, r) != 0 || r.family != FAM_RING || r.em[0] != EM_DRELU) return 0;
   return (a->M + 127) / 128;
 }
 
 extern "C" int64_t nstl_gemm_relu_mask_words(const nstl_gemm_args* a) {
-  GemmParams p;
-  if (a == nullptr || make_params(a, p) != 0) return 0;
-  if (a->dtype == NSTL_FP8) {
-    const int em = ring_epi_mode(a, p);
-    if (a->split_k > 1 || a->c_dtype != NSTL_BF16 || (em != EM_RELU_DROP && em != EM_DRELU)) return 0;
-    return (int64_t)((a->M + 63) / 64) * 8 * ((a->N + 7) / 8);
-  }
-  if (!big_ok(a) || a->split_k > 1 || a->dtype != NSTL_BF16 || a->c_dtype != NSTL_BF16) return 0;
-  const int em = ring_epi_mode(a, p);
-  if (em != EM_RELU_DROP && em != EM_DRELU) return 0;
+  Route r;
+  if (route(a, nullptr, r) != 0 || r.family != FAM_RING || (r.em[0] != EM_RELU_DROP && r.em[0] != EM_DRELU)) return 0;
   return (int64_t)((a->M + 63) / 64) * 8 * ((a->N + 7) / 8);
 }
