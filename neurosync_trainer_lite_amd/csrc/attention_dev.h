@@ -8,6 +8,10 @@
 // each file's own.  AttnParams crosses from attention.hip's entry points to
 // attention_long.hip's launchers, so it has a name (nstl::); everything else sits
 // in the including file's anonymous namespace, next to its kernels.
+// DH = 64 is the width of one operand image and of one result tile.  The streaming
+// kernels also take head_dim 128 as two such halves, and reuse every helper here per
+// half; only RoPE^T knows the head's width (the pair index offset of the half and the
+// frequency divisor: rope_tab's i0, rope_tab_fast<DHT>, rope_back_tile<DHT>).
 #pragma once
 #include "common.h"
 #include "status.h"
@@ -23,7 +27,7 @@ struct AttnParams {
   float* lse;
   float* dsum;
   uint64_t* mask;  // dropout keep bits (fast path), see mask_word()
-  float* dbias;    // optional [B * nblk][3 * H * DH] column sums of dq | dk | dv (fast path)
+  float* dbias;    // optional [B * nblk][3 * H * dh] column sums of dq | dk | dv (fast path)
   const char* dout; int64_t dout_ld;
   char* dq; int64_t dq_ld;
   char* dk; int64_t dk_ld;
@@ -212,12 +216,13 @@ NSTL_DEV float swap_pair(float v) {
 // folded in (ts = -sin on odd lanes), so every element is x cos + partner ts:
 // one multiply and one FMA.  rope_apply needs every lane of the wave active.
 template <int RS>
-NSTL_DEV void rope_tab(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, const float* cs, const float* sn) {
+NSTL_DEV void rope_tab(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, const float* cs, const float* sn,
+                       int i0 = 0) {
 #pragma unroll
   for (int r = 0; r < 4; ++r)
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
-      const int i = (row0 + r) * RS + dt * 8 + (c >> 1);
+      const int i = (row0 + r) * RS + i0 + dt * 8 + (c >> 1);
       tc[dt][r] = cs[i];
       ts[dt][r] = (c & 1) ? -sn[i] : sn[i];
     }
@@ -225,13 +230,13 @@ NSTL_DEV void rope_tab(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, co
 // rope_tab with the table row clamped to row_last (a ragged head's last wave: its
 // rows past the head hold zeros, but the tables end at row T - 1)
 template <int RS>
-NSTL_DEV void rope_tab(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, const float* cs, const float* sn,
-                       int row_last) {
+NSTL_DEV void rope_tab_clamped(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, const float* cs, const float* sn,
+                               int row_last, int i0 = 0) {
 #pragma unroll
   for (int r = 0; r < 4; ++r)
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
-      const int i = min(row0 + r, row_last) * RS + dt * 8 + (c >> 1);
+      const int i = min(row0 + r, row_last) * RS + i0 + dt * 8 + (c >> 1);
       tc[dt][r] = cs[i];
       ts[dt][r] = (c & 1) ? -sn[i] : sn[i];
     }
@@ -253,12 +258,15 @@ NSTL_DEV void rope_apply(float (&v)[4][4], const float (&tc)[4][4], const float 
 // The angle goes to v_sin / v_cos in revolutions, t * (inv_freq / 2pi), with the
 // lane's sign folded into the factor (sin is odd, cos even): one multiply per
 // angle instead of three (angle, 1/2pi for each of sin and cos, the sign).
-NSTL_DEV void rope_tab_fast(float (&tc)[4][4], float (&ts)[4][4], int row0, int c) {
+// DHT: the head width (the divisor of the frequency exponent); i0: the first pair
+// index of the tile (32 for columns 64..127 of a 128-wide head).
+template <int DHT = DH>
+NSTL_DEV void rope_tab_fast(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, int i0 = 0) {
   const float sgn_rev = ((c & 1) ? -1.f : 1.f) * 0.15915494309189535f;  // +-1/(2pi)
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
-    const float two_i = (float)(2 * (dt * 8 + (c >> 1)));
-    const float inv_freq = __expf(-9.21034049987793f * two_i / (float)DH);  // f32(ln 10000)
+    const float two_i = (float)(2 * (i0 + dt * 8 + (c >> 1)));
+    const float inv_freq = __expf(-9.21034049987793f * two_i / (float)DHT);  // f32(ln 10000)
     const float f = inv_freq * sgn_rev;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -271,18 +279,23 @@ NSTL_DEV void rope_tab_fast(float (&tc)[4][4], float (&ts)[4][4], int row0, int 
 // fast: the angles recomputed (rope_tab_fast) instead of per-element table reads
 // from global memory (16 dependent L2 round trips per wave at the end of the split
 // kernels; bf16 only -- the f32 parity mode keeps the tables' exact values)
-NSTL_DEV void rope_back_tile(float (&v)[4][4], int row0, int c, const float* cs, const float* sn, bool fast = false) {
+// The tile is columns 64 hf .. 64 hf + 63 of a DHT-wide head: pair indices
+// 32 hf + 8 dt + (c >> 1) of the head's DHT / 2, table row stride DHT / 2.
+template <int DHT = DH>
+NSTL_DEV void rope_back_tile(float (&v)[4][4], int row0, int c, const float* cs, const float* sn, bool fast = false,
+                             int hf = 0) {
   float tc[4][4], ts[4][4];
-  if (fast) rope_tab_fast(tc, ts, row0, c);
-  else rope_tab<DH / 2>(tc, ts, row0, c, cs, sn);
+  if (fast) rope_tab_fast<DHT>(tc, ts, row0, c, 32 * hf);
+  else rope_tab<DHT / 2>(tc, ts, row0, c, cs, sn, 32 * hf);
   rope_apply(v, tc, ts);
 }
-
-NSTL_DEV void rope_back_tile(float (&v)[4][4], int row0, int c, const float* cs, const float* sn, bool fast,
-                             int row_last) {
+// ... with the table row clamped to row_last (rope_tab_clamped)
+template <int DHT = DH>
+NSTL_DEV void rope_back_tile_clamped(float (&v)[4][4], int row0, int c, const float* cs, const float* sn, bool fast,
+                                     int row_last, int hf = 0) {
   float tc[4][4], ts[4][4];
-  if (fast) rope_tab_fast(tc, ts, row0, c);
-  else rope_tab<DH / 2>(tc, ts, row0, c, cs, sn, row_last);
+  if (fast) rope_tab_fast<DHT>(tc, ts, row0, c, 32 * hf);
+  else rope_tab_clamped<DHT / 2>(tc, ts, row0, c, cs, sn, row_last, 32 * hf);
   rope_apply(v, tc, ts);
 }
 

@@ -2,7 +2,17 @@
 // 256 < T <= 4096): the shapes past the one-shot kernels of attention.hip, whose
 // score rows live in registers and whose K / V of a whole head live in LDS; and,
 // for a caller that sets NSTL_ATTN_RAGGED_OK, for every ragged window (T % 32 != 0,
-// 1 <= T <= 4096), which the one-shot kernels do not take at any length.
+// 1 <= T <= 4096), which the one-shot kernels do not take at any length; and, for a
+// caller that sets NSTL_ATTN_DH128_OK, for head_dim 128 at every window length (the
+// one-shot kernels are head_dim 64 only).
+//
+// The head width is the template parameter DHT of the three kernels (64 or 128).  A
+// 128-wide head is two 64-column halves: every K / V / Q / dO tile is two
+// 128-byte-row images (columns 0..63 and 64..127) with the swizzle, the DMA pieces
+// and the reads of the 64-wide case; scores and dP sum four 32-wide k-chunks instead
+// of two; O, dQ, dK and dV are two groups of four 16-column accumulator tiles, stored,
+// rotated (RoPE^T pair index 32 half + ...) and column-summed one half at a time.  The
+// <64, ...> instantiations are the kernels as they were before DHT.
 //
 // Here nothing of size T x T or T per lane is held.  Every kernel owns a block of
 // 128 rows of one (batch, head) -- 8 waves, 16 rows each, the wave's own rows
@@ -50,33 +60,61 @@ namespace {
 
 constexpr int LNT = 512, NW = LNT / 64, ROWS = 16 * NW;  // 8 waves, 128 rows per workgroup
 constexpr int KT = 64;                                    // streamed rows per tile
-constexpr int TILE_B = KT * DH * 2, BUF_B = 2 * TILE_B;   // one image 8 KB; a buffer holds two
+constexpr int TILE_B = KT * 64 * 2;                       // one 64-column image: 8 KB
+// A DHT-wide operand tile is NH = DHT / 64 images side by side (columns 64 hf ..
+// 64 hf + 63 in image hf), each an ImgAtt<128> of its own; a buffer holds two
+// operands: [A images][B images].
+template <int DHT> struct Geo {
+  static_assert(DHT == 64 || DHT == 128, "head widths of the streaming kernels");
+  static constexpr int NH = DHT / 64, OP_B = NH * TILE_B, BUF_B = 2 * OP_B;
+  // waves per SIMD the forward and dQ kernels are compiled for
+  static constexpr int OCC = DHT == 64 ? 4 : 2;
+};
 constexpr int LONG_MIN_T = 256, LONG_MAX_T = 4096;        // (one-shot limit, T range of nstl_attn]
+
+// f(half 0), then f(half 1) of a 128-wide head, the half a compile-time constant (the
+// backward epilogues).  In the backward tile loops the second half is instead an
+// `if constexpr (NH == 2)` block behind the 64-wide statements: as a loop over halves
+// or through this helper the 64-wide kernels came out with other register counts
+// (DESIGN.md section 4), as written they have the counts they had before DHT.
+template <int V> struct HalfC { static constexpr int value = V; };
+template <int NH, typename F>
+NSTL_DEV void for_halves(F&& f) {
+  f(HalfC<0>{});
+  if constexpr (NH == 2) f(HalfC<1>{});
+}
 
 NSTL_DEV f32x4 asm_f32x4(const float* p) {
   f32x4 v;
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr((const char*)p)));
   return v;
 }
-// This wave's 1 KB piece (rows 8w .. 8w + 7) of tile t of two operands into buffer
-// buf: image A at the buffer's start, image B behind it.  The source row is clamped
+// This wave's 1 KB pieces (rows 8w .. 8w + 7 of every image) of tile t of two operands
+// into buffer buf: A's images at the buffer's start, B's behind them.  The source row
+// is clamped
 // to the head's last row (a partial last tile re-reads row T - 1: finite data, never
 // past the head).
-struct TileDma {
+template <int DHT> struct TileDma {
+  static constexpr int NH = Geo<DHT>::NH, OP_B = Geo<DHT>::OP_B, BUF_B = Geo<DHT>::BUF_B;
   const char* a; int64_t a_ldb;
   const char* b; int64_t b_ldb;
   int lrow, lc, T;
   NSTL_DEV void issue(char* smem, int t, int buf, int w) const {
     const int row = min(t * KT + lrow, T - 1);
-    dma1k(a + row * a_ldb + lc * 16, smem + buf * BUF_B + w * 1024);
-    dma1k(b + row * b_ldb + lc * 16, smem + buf * BUF_B + TILE_B + w * 1024);
+#pragma unroll
+    for (int hf = 0; hf < NH; ++hf)
+      dma1k(a + row * a_ldb + hf * 128 + lc * 16, smem + buf * BUF_B + hf * TILE_B + w * 1024);
+#pragma unroll
+    for (int hf = 0; hf < NH; ++hf)
+      dma1k(b + row * b_ldb + hf * 128 + lc * 16, smem + buf * BUF_B + OP_B + hf * TILE_B + w * 1024);
   }
 };
-NSTL_DEV TileDma tile_dma(const char* a, int64_t a_ld, const char* b, int64_t b_ld, int64_t tok0, int h, int T, int w,
-                          int lane) {
-  TileDma d;
-  d.a = a + (tok0 * a_ld + h * DH) * 2; d.a_ldb = a_ld * 2;
-  d.b = b + (tok0 * b_ld + h * DH) * 2; d.b_ldb = b_ld * 2;
+template <int DHT>
+NSTL_DEV TileDma<DHT> tile_dma(const char* a, int64_t a_ld, const char* b, int64_t b_ld, int64_t tok0, int h, int T,
+                               int w, int lane) {
+  TileDma<DHT> d;
+  d.a = a + (tok0 * a_ld + h * DHT) * 2; d.a_ldb = a_ld * 2;
+  d.b = b + (tok0 * b_ld + h * DHT) * 2; d.b_ldb = b_ld * 2;
   d.lrow = w * 8 + (lane >> 3);
   d.lc = (lane & 7) ^ att_x(d.lrow);
   d.T = T;
@@ -88,9 +126,10 @@ NSTL_DEV TileDma tile_dma(const char* a, int64_t a_ld, const char* b, int64_t b_
 // 16 scores of ITS query per tile, the rest are in the lanes c + 16 g' (two
 // permlane swaps for the tile maximum).  The running sum stays a per-lane partial
 // (the four lanes of a query rescale by the same factor) and is reduced once at
-// the end.  LDS: 2 x (K | V) = 32 KB.
-template <bool DROP, bool RAG = false>
-__global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
+// the end.  LDS: 2 x (K | V) = 32 KB (head_dim 64) / 64 KB (128).
+template <int DHT, bool DROP, bool RAG = false>
+__global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_fwd_long_kernel(AttnParams p) {
+  constexpr int NH = Geo<DHT>::NH, OP_B = Geo<DHT>::OP_B, BUF_B = Geo<DHT>::BUF_B;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
@@ -99,23 +138,23 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
   const int64_t tok0 = (int64_t)b * T_;
   const int q0 = blockIdx.x * ROWS + w * 16;
   const bool act = q0 < T_;
-  const TileDma dma = tile_dma(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
+  const TileDma<DHT> dma = tile_dma<DHT>(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
   dma.issue(smem, 0, 0, w);
   // RAG: a wave that straddles T reads its rows past the head from row T - 1 and
   // stores nothing for them
   const int qr = RAG ? min(q0 + c, T_ - 1) : q0 + c;
   const bool qok = !RAG || q0 + c < T_;
-  bf16x8 fq[2] = {};
+  bf16x8 fq[2 * NH] = {};  // elements 32 u + 8g .. + 7 of the query's row, u = 0 .. 2 NH - 1
   if (act) {
-    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DH;
-    fq[0] = *(const bf16x8*)(qrow + 8 * g);
-    fq[1] = *(const bf16x8*)(qrow + 32 + 8 * g);
+    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DHT;
+#pragma unroll
+    for (int u = 0; u < 2 * NH; ++u) fq[u] = *(const bf16x8*)(qrow + 32 * u + 8 * g);
   }
   const float c2 = p.scale * LOG2E;
   float m = -INFINITY, lsum = 0.f;
-  f32x4 o[4];
+  f32x4 o[4 * NH];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < 4 * NH; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const uint32_t st = nstl_seed_term(p.seed);
   for (int t = 0; t < ntile; ++t) {
     vmcnt_wait<0>();          // this wave's piece of tile t (and its stores of tile t-1)
@@ -123,20 +162,26 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
     if (t + 1 < ntile) dma.issue(smem, t + 1, (t + 1) & 1, w);
     if (!act) continue;
     const char* Kimg = smem + (t & 1) * BUF_B;
-    const char* Vimg = Kimg + TILE_B;
+    const char* Vimg = Kimg + OP_B;
     const int kb = t * KT;
     f32x4 s[4];
 #pragma unroll
     for (int kt = 0; kt < 4; kt += 2) {
-      bf16x8 fk[4];
+      bf16x8 fk[4 * NH];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) asm_row128(fk[u], Kimg, (kt + (u >> 1)) * 16 + c, 32 * (u & 1) + 8 * g);
+      for (int hf = 0; hf < NH; ++hf)
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          asm_row128(fk[4 * hf + u], Kimg + hf * TILE_B, (kt + (u >> 1)) * 16 + c, 32 * (u & 1) + 8 * g);
       lgkm_fence();
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         s[kt + u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        mma16(s[kt + u], fk[2 * u], fq[0]);
-        mma16(s[kt + u], fk[2 * u + 1], fq[1]);
+#pragma unroll
+        for (int hf = 0; hf < NH; ++hf) {
+          mma16(s[kt + u], fk[4 * hf + 2 * u], fq[2 * hf]);
+          mma16(s[kt + u], fk[4 * hf + 2 * u + 1], fq[2 * hf + 1]);
+        }
       }
     }
     if (kb + KT > T_) {  // the partial last tile: keys past T get probability 0
@@ -157,7 +202,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
     m = mn;
     lsum *= alpha;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
+    for (int dt = 0; dt < 4 * NH; ++dt) o[dt] *= alpha;
     const float nmc = -mn * c2;
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt)
@@ -227,12 +272,15 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const bf16x8 fp = acc_frag<bf16>(s[2 * j], s[2 * j + 1]);
-      bf16x8 fv[4];
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) asm_col2_128(fv[dt], Vimg, dt * 16, 32 * j, lane);
-      lgkm_fence();
+      for (int hf = 0; hf < NH; ++hf) {
+        bf16x8 fv[4];
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) mma16(o[dt], fv[dt], fp);
+        for (int dt = 0; dt < 4; ++dt) asm_col2_128(fv[dt], Vimg + hf * TILE_B, dt * 16, 32 * j, lane);
+        lgkm_fence();
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) mma16(o[4 * hf + dt], fv[dt], fp);
+      }
     }
   }
   if (!act) return;
@@ -240,9 +288,9 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
   sum = sum_xor32(sum);
   const float inv = (DROP ? p.inv_keep : 1.f) * __builtin_amdgcn_rcpf(sum);
   if (!qok) return;
-  bf16* orow = (bf16*)p.o + (tok0 + q0 + c) * p.o_ld + h * DH + 4 * g;
+  bf16* orow = (bf16*)p.o + (tok0 + q0 + c) * p.o_ld + h * DHT + 4 * g;
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
+  for (int dt = 0; dt < 4 * NH; ++dt) {
     const f32x4 x = o[dt] * inv;
     *(bf16x4*)(orow + 16 * dt) = (bf16x4){(bf16)x[0], (bf16)x[1], (bf16)x[2], (bf16)x[3]};
   }
@@ -253,14 +301,18 @@ __global__ __launch_bounds__(LNT, 4) void attn_fwd_long_kernel(AttnParams p) {
 // dQ.  Workgroup = (b, h, 128 queries); K / V tiles stream.  DM: dropout mode
 // (0 none, 1 the forward's stored keep bits, 2 re-hashed).  LDS: 2 x (K | V) =
 // 32 KB (the output staging reuses it after the sweep), bias partials, counter.
-constexpr int DQ_RED_OFF = 2 * BUF_B, DQ_ARR_OFF = DQ_RED_OFF + NW * 64 * 4;
-constexpr size_t DQ_LDS = DQ_ARR_OFF + 16;
+// (head_dim 128: 64 KB, and one bias partial array [NW][64] per 64-column half.)
+template <int DHT> struct DqLds {
+  static constexpr int RED_OFF = 2 * Geo<DHT>::BUF_B, ARR_OFF = RED_OFF + Geo<DHT>::NH * NW * 64 * 4;
+  static constexpr size_t BYTES = ARR_OFF + 16;
+};
 
-template <int DM, bool RAG = false>
-__global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) {
+template <int DHT, int DM, bool RAG = false>
+__global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(AttnParams p) {
+  constexpr int NH = Geo<DHT>::NH, OP_B = Geo<DHT>::OP_B, BUF_B = Geo<DHT>::BUF_B;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = (float*)(smem + DQ_RED_OFF);
-  unsigned* arrived = (unsigned*)(smem + DQ_ARR_OFF);
+  float* red = (float*)(smem + DqLds<DHT>::RED_OFF);  // [NH][NW][64]
+  unsigned* arrived = (unsigned*)(smem + DqLds<DHT>::ARR_OFF);
   const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -268,7 +320,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
   const int64_t tok0 = (int64_t)b * T_;
   const int q0 = blockIdx.x * ROWS + w * 16;
   const bool act = q0 < T_;
-  const TileDma dma = tile_dma(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
+  const TileDma<DHT> dma = tile_dma<DHT>(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
   dma.issue(smem, 0, 0, w);
   // stored keep bits of this wave's 16 queries against tile t: lane kt * 4 + r holds word (kt, r)
   auto load_mask = [&](int t) -> uint64_t {
@@ -276,7 +328,7 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
     if (lane < 4 * min(4, nt16 - kt0)) return p.mask[mask_word(bh, nt16, q0 >> 4, kt0, 0) + lane];
     return 0;
   };
-  bf16x8 fq[2] = {}, fo[2] = {};
+  bf16x8 fq[2 * NH] = {}, fo[2 * NH] = {};
   float lq = 0.f, dqv = 0.f;  // LSE (log2 units) and D of this lane's query q0 + c
   uint64_t mcur = 0, mnext = 0;
   // RAG: queries past T of a straddling wave read row T - 1, carry lq = +inf (P = 0)
@@ -284,19 +336,19 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
   const int qr = RAG ? min(q0 + c, T_ - 1) : q0 + c;
   const bool qok = !RAG || q0 + c < T_;
   if (act) {
-    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DH;
-    const bf16* drow = (const bf16*)p.dout + (tok0 + qr) * p.dout_ld + h * DH;
-    const bf16* orow = (const bf16*)p.o + (tok0 + qr) * p.o_ld + h * DH;
-    bf16x8 oo[2];
+    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DHT;
+    const bf16* drow = (const bf16*)p.dout + (tok0 + qr) * p.dout_ld + h * DHT;
+    const bf16* orow = (const bf16*)p.o + (tok0 + qr) * p.o_ld + h * DHT;
+    bf16x8 oo[2 * NH];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < 2 * NH; ++u) {
       fq[u] = *(const bf16x8*)(qrow + 32 * u + 8 * g);
       fo[u] = *(const bf16x8*)(drow + 32 * u + 8 * g);
       oo[u] = *(const bf16x8*)(orow + 32 * u + 8 * g);
     }
     float dpart = 0.f;
 #pragma unroll
-    for (int u = 0; u < 2; ++u)
+    for (int u = 0; u < 2 * NH; ++u)
 #pragma unroll
       for (int e = 0; e < 8; ++e) dpart += (float)fo[u][e] * (float)oo[u][e];
     dpart = sum_xor16(dpart);
@@ -308,9 +360,9 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
   }
   if (tid == 0) *arrived = 0u;
   const float c2 = p.scale * LOG2E;
-  f32x4 dq[4];
+  f32x4 dq[4 * NH];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < 4 * NH; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int t = 0; t < ntile; ++t) {
     vmcnt_wait<0>();
     __syncthreads();
@@ -320,12 +372,13 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
     }
     if (!act) continue;
     const char* Kimg = smem + (t & 1) * BUF_B;
-    const char* Vimg = Kimg + TILE_B;
+    const char* Vimg = Kimg + OP_B;
     const int nc = min(2, (T_ - t * KT + (RAG ? 31 : 0)) / 32);  // 32-key chunks with a valid key
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if (j < nc) {
-        bf16x8 fb[8];
+        // fb[8 hf + 4 u + x]: x = 0, 1: K elements 64 hf + 32 x + 8g ..; x = 2, 3: V's
+        bf16x8 fb[8 * NH];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const int row = (2 * j + u) * 16 + c;
@@ -333,6 +386,12 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
           asm_row128(fb[4 * u + 1], Kimg, row, 32 + 8 * g);
           asm_row128(fb[4 * u + 2], Vimg, row, 8 * g);
           asm_row128(fb[4 * u + 3], Vimg, row, 32 + 8 * g);
+          if constexpr (NH == 2) {
+            asm_row128(fb[8 + 4 * u + 0], Kimg + TILE_B, row, 8 * g);
+            asm_row128(fb[8 + 4 * u + 1], Kimg + TILE_B, row, 32 + 8 * g);
+            asm_row128(fb[8 + 4 * u + 2], Vimg + TILE_B, row, 8 * g);
+            asm_row128(fb[8 + 4 * u + 3], Vimg + TILE_B, row, 32 + 8 * g);
+          }
         }
         lgkm_fence();
         f32x4 dsv[2];
@@ -342,8 +401,16 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
           f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
           mma16(sc, fb[4 * u + 0], fq[0]);
           mma16(sc, fb[4 * u + 1], fq[1]);
+          if constexpr (NH == 2) {
+            mma16(sc, fb[8 + 4 * u + 0], fq[2]);
+            mma16(sc, fb[8 + 4 * u + 1], fq[3]);
+          }
           mma16(dp, fb[4 * u + 2], fo[0]);
           mma16(dp, fb[4 * u + 3], fo[1]);
+          if constexpr (NH == 2) {
+            mma16(dp, fb[8 + 4 * u + 2], fo[2]);
+            mma16(dp, fb[8 + 4 * u + 3], fo[3]);
+          }
           // sc[r] / dp[r]: S^T / dP^T at (key 16 kt + 4g + r, query q0 + c)
           bool keep[4] = {true, true, true, true};
           if constexpr (DM == 1) {
@@ -375,36 +442,55 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
         lgkm_fence();
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) mma16(dq[dt], fa, fc[dt]);
+        if constexpr (NH == 2) {  // columns 64 .. 127
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) asm_col2_128(fc[dt], Kimg + TILE_B, dt * 16, 32 * j, lane);
+          lgkm_fence();
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) mma16(dq[4 + dt], fa, fc[dt]);
+        }
       }
     }
     mcur = mnext;
   }
   __syncthreads();  // every wave is done with the tiles: the buffers become output staging
-  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * DH : nullptr;
+  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * DHT : nullptr;
   if (!act) {
     if (bias_row) {
-      red[w * 64 + lane] = 0.f;
-      if (last_to_arrive(arrived, NW, lane)) wave_sum_out(red, NW, bias_row + h * DH, lane);
+#pragma unroll
+      for (int hf = 0; hf < NH; ++hf) red[hf * NW * 64 + w * 64 + lane] = 0.f;
+      if (last_to_arrive(arrived, NW, lane)) {
+#pragma unroll
+        for (int hf = 0; hf < NH; ++hf) wave_sum_out(red + hf * NW * 64, NW, bias_row + h * DHT + 64 * hf, lane);
+      }
     }
     return;
   }
-  float vq[4][4];
+  // the wave's 16 x DHT result, one 16 x 64 tile per half through the same staging
+  for_halves<NH>([&](auto HF) __attribute__((always_inline)) {
+    constexpr int hf = decltype(HF)::value;
+    float vq[4][4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r)
+    for (int r = 0; r < 4; ++r)
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vq[dt][r] = dq[dt][r] * p.scale;
-  char* dq_dst = p.dq + ((tok0 + q0) * p.dq_ld + h * DH) * 2;
-  if constexpr (RAG) {
-    if (p.rope_q) rope_back_tile(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1);
-    store_tile16x64<bf16>(vq, smem + w * 2048, dq_dst, p.dq_ld, lane, T_ - q0);
-  } else {
-    if (p.rope_q) rope_back_tile(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
-    store_tile16x64<bf16>(vq, smem + w * 2048, dq_dst, p.dq_ld, lane);
-  }
-  if (bias_row) {
-    wave_colsum16x64<bf16>(vq, red, w, lane);
-    if (last_to_arrive(arrived, NW, lane)) wave_sum_out(red, NW, bias_row + h * DH, lane);
-  }
+      for (int dt = 0; dt < 4; ++dt) vq[dt][r] = dq[4 * hf + dt][r] * p.scale;
+    char* dq_dst = p.dq + ((tok0 + q0) * p.dq_ld + h * DHT + 64 * hf) * 2;
+    if constexpr (RAG) {
+      if (p.rope_q)
+        rope_back_tile_clamped<DHT>(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1, hf);
+      store_tile16x64<bf16>(vq, smem + w * 2048, dq_dst, p.dq_ld, lane, T_ - q0);
+    } else {
+      if (p.rope_q) rope_back_tile<DHT>(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, hf);
+      store_tile16x64<bf16>(vq, smem + w * 2048, dq_dst, p.dq_ld, lane);
+    }
+    if (bias_row) {
+      wave_colsum16x64<bf16>(vq, red + hf * NW * 64, w, lane);
+      if (hf == NH - 1 && last_to_arrive(arrived, NW, lane)) {
+#pragma unroll
+        for (int h2 = 0; h2 < NH; ++h2) wave_sum_out(red + h2 * NW * 64, NW, bias_row + h * DHT + 64 * h2, lane);
+      }
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -414,27 +500,31 @@ __global__ __launch_bounds__(LNT, 4) void attn_bwd_dq_long_kernel(AttnParams p) 
 // staging), lse | D (8 T bytes), bias partials, counter.
 // rows of each of the LSE / D arrays: T, or (ragged T) T rounded up to whole
 // 64-query tiles -- the padding rows hold lse = +inf / D = 0, and both arrays stay
-// 16-byte aligned for ds_read_b128
+// 16-byte aligned for ds_read_b128.  head_dim 128: the tile buffers are 64 KB and
+// the bias partials [dk | dv][half][NW][64]; 104 KB at T = 4096.
 int dkv_rows(int T) { return T % 32 == 0 ? T : (T + KT - 1) / KT * KT; }
-NSTL_DEV int dkv_red_off(int rows) { return 2 * BUF_B + 2 * rows * 4; }
-size_t dkv_lds_bytes(int T) { return (size_t)2 * BUF_B + (size_t)2 * dkv_rows(T) * 4 + 2 * NW * 64 * 4 + 16; }
+template <int DHT> NSTL_DEV int dkv_red_off(int rows) { return 2 * Geo<DHT>::BUF_B + 2 * rows * 4; }
+template <int DHT> size_t dkv_lds_bytes(int T) {
+  return (size_t)2 * Geo<DHT>::BUF_B + (size_t)2 * dkv_rows(T) * 4 + 2 * Geo<DHT>::NH * NW * 64 * 4 + 16;
+}
 
-template <int DM, bool RAG = false>
+template <int DHT, int DM, bool RAG = false>
 __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
+  constexpr int NH = Geo<DHT>::NH, OP_B = Geo<DHT>::OP_B, BUF_B = Geo<DHT>::BUF_B;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
   const int Tp = RAG ? ntile * KT : T_;  // dkv_rows(T)
   float* lse_s = (float*)(smem + 2 * BUF_B);
   float* dq_s = lse_s + Tp;
-  float* red = (float*)(smem + dkv_red_off(Tp));  // [2][NW][64]
-  unsigned* arrived = (unsigned*)(red + 2 * NW * 64);
+  float* red = (float*)(smem + dkv_red_off<DHT>(Tp));  // [2][NH][NW][64]
+  unsigned* arrived = (unsigned*)(red + 2 * NH * NW * 64);
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
   const int64_t tok0 = (int64_t)b * T_;
   const int k0 = blockIdx.x * ROWS + w * 16;
   const bool act = k0 < T_;
-  const TileDma dma = tile_dma(p.q, p.q_ld, p.dout, p.dout_ld, tok0, h, T_, w, lane);
+  const TileDma<DHT> dma = tile_dma<DHT>(p.q, p.q_ld, p.dout, p.dout_ld, tok0, h, T_, w, lane);
   dma.issue(smem, 0, 0, w);
   if constexpr (RAG) {  // queries past T: P = 2^(s - inf) = 0 and dS = 0 * (dP - 0) = 0
     for (int i = tid; i < Tp; i += LNT) {
@@ -453,17 +543,17 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
     if (lane < 16 && qt < nt16) return p.mask[mask_word(bh, nt16, qt, k0 >> 4, lane & 3)];
     return 0;
   };
-  bf16x8 fk[2] = {}, fv[2] = {};
+  bf16x8 fk[2 * NH] = {}, fv[2 * NH] = {};
   uint64_t mcur = 0, mnext = 0;
   // RAG: keys past T of a straddling wave read row T - 1 and get P = 0 below, so
   // their dK / dV rows are exactly 0; they store nothing
   const int kr = RAG ? min(k0 + c, T_ - 1) : k0 + c;
   const bool kok = !RAG || k0 + c < T_;
   if (act) {
-    const bf16* krow = (const bf16*)p.k + (tok0 + kr) * p.k_ld + h * DH;
-    const bf16* vrow = (const bf16*)p.v + (tok0 + kr) * p.v_ld + h * DH;
+    const bf16* krow = (const bf16*)p.k + (tok0 + kr) * p.k_ld + h * DHT;
+    const bf16* vrow = (const bf16*)p.v + (tok0 + kr) * p.v_ld + h * DHT;
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < 2 * NH; ++u) {
       fk[u] = *(const bf16x8*)(krow + 32 * u + 8 * g);
       fv[u] = *(const bf16x8*)(vrow + 32 * u + 8 * g);
     }
@@ -471,9 +561,9 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   }
   if (tid == 0) *arrived = 0u;
   const float c2 = p.scale * LOG2E;
-  f32x4 dk[4], dv[4];
+  f32x4 dk[4 * NH], dv[4 * NH];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) dk[dt] = dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < 4 * NH; ++dt) dk[dt] = dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int t = 0; t < ntile; ++t) {
     vmcnt_wait<0>();
     __syncthreads();
@@ -483,12 +573,13 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
     }
     if (!act) continue;
     const char* Qimg = smem + (t & 1) * BUF_B;
-    const char* Dimg = Qimg + TILE_B;
+    const char* Dimg = Qimg + OP_B;
     const int nc = min(2, (T_ - t * KT + (RAG ? 31 : 0)) / 32);  // 32-query chunks with a valid query
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if (j < nc) {
-        bf16x8 fb[8];
+        // fb[8 hf + 4 u + x]: x = 0, 1: Q elements 64 hf + 32 x + 8g ..; x = 2, 3: dO's
+        bf16x8 fb[8 * NH];
         f32x4 l4[2], d4[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -497,6 +588,12 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
           asm_row128(fb[4 * u + 1], Qimg, row, 32 + 8 * g);
           asm_row128(fb[4 * u + 2], Dimg, row, 8 * g);
           asm_row128(fb[4 * u + 3], Dimg, row, 32 + 8 * g);
+          if constexpr (NH == 2) {
+            asm_row128(fb[8 + 4 * u + 0], Qimg + TILE_B, row, 8 * g);
+            asm_row128(fb[8 + 4 * u + 1], Qimg + TILE_B, row, 32 + 8 * g);
+            asm_row128(fb[8 + 4 * u + 2], Dimg + TILE_B, row, 8 * g);
+            asm_row128(fb[8 + 4 * u + 3], Dimg + TILE_B, row, 32 + 8 * g);
+          }
           const int qb = t * KT + (2 * j + u) * 16 + 4 * g;  // this lane's four queries
           l4[u] = asm_f32x4(lse_s + qb);
           d4[u] = asm_f32x4(dq_s + qb);
@@ -509,8 +606,16 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
           f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
           mma16(st, fb[4 * u + 0], fk[0]);
           mma16(st, fb[4 * u + 1], fk[1]);
+          if constexpr (NH == 2) {
+            mma16(st, fb[8 + 4 * u + 0], fk[2]);
+            mma16(st, fb[8 + 4 * u + 1], fk[3]);
+          }
           mma16(dpt, fb[4 * u + 2], fv[0]);
           mma16(dpt, fb[4 * u + 3], fv[1]);
+          if constexpr (NH == 2) {
+            mma16(dpt, fb[8 + 4 * u + 2], fv[2]);
+            mma16(dpt, fb[8 + 4 * u + 3], fv[3]);
+          }
           // keep bits of (queries 4g + r, key k0 + c): 4 consecutive bits of word (qtl, key % 4)
           uint32_t nib = 0;
           if (DM == 1) nib = (uint32_t)(shfl64(mcur, 4 * qtl + (lane & 3)) >> (16 * (c >> 2) + 4 * g));
@@ -543,62 +648,107 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
           mma16(dv[dt], fa1, fc[2 * dt]);
           mma16(dk[dt], fa2, fc[2 * dt + 1]);
         }
+        if constexpr (NH == 2) {  // columns 64 .. 127
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) {
+            asm_col2_128(fc[2 * dt], Dimg + TILE_B, dt * 16, 32 * j, lane);
+            asm_col2_128(fc[2 * dt + 1], Qimg + TILE_B, dt * 16, 32 * j, lane);
+          }
+          lgkm_fence();
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) {
+            mma16(dv[4 + dt], fa1, fc[2 * dt]);
+            mma16(dk[4 + dt], fa2, fc[2 * dt + 1]);
+          }
+        }
       }
     }
     mcur = mnext;
   }
   __syncthreads();  // every wave is done with the tiles: the buffers become output staging
-  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * DH : nullptr;
+  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * DHT : nullptr;
+  float* red_v = red + NH * NW * 64;
   if (!act) {
     if (bias_row) {
-      red[w * 64 + lane] = 0.f;
-      red[NW * 64 + w * 64 + lane] = 0.f;
+#pragma unroll
+      for (int hf = 0; hf < NH; ++hf) {
+        red[hf * NW * 64 + w * 64 + lane] = 0.f;
+        red_v[hf * NW * 64 + w * 64 + lane] = 0.f;
+      }
       if (last_to_arrive(arrived, NW, lane)) {
-        wave_sum_out(red, NW, bias_row + p.H * DH + h * DH, lane);
-        wave_sum_out(red + NW * 64, NW, bias_row + 2 * p.H * DH + h * DH, lane);
+#pragma unroll
+        for (int hf = 0; hf < NH; ++hf) {
+          wave_sum_out(red + hf * NW * 64, NW, bias_row + p.H * DHT + h * DHT + 64 * hf, lane);
+          wave_sum_out(red_v + hf * NW * 64, NW, bias_row + 2 * p.H * DHT + h * DHT + 64 * hf, lane);
+        }
       }
     }
     return;
   }
-  float vk[4][4], vv[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      vk[dt][r] = dk[dt][r] * p.scale;
-      vv[dt][r] = DM != 0 ? dv[dt][r] * p.inv_keep : dv[dt][r];
-    }
+  // the wave's two 16 x DHT results, one 16 x 64 tile per half through the same staging
   char* scr = smem + w * 2048;
-  char* dk_dst = p.dk + ((tok0 + k0) * p.dk_ld + h * DH) * 2;
-  char* dv_dst = p.dv + ((tok0 + k0) * p.dv_ld + h * DH) * 2;
-  if constexpr (RAG) {
-    if (p.rope_k) rope_back_tile(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1);
-    store_tile16x64<bf16>(vk, scr, dk_dst, p.dk_ld, lane, T_ - k0);
-    store_tile16x64<bf16>(vv, scr, dv_dst, p.dv_ld, lane, T_ - k0);
-  } else {
-    if (p.rope_k) rope_back_tile(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast);
-    store_tile16x64<bf16>(vk, scr, dk_dst, p.dk_ld, lane);
-    store_tile16x64<bf16>(vv, scr, dv_dst, p.dv_ld, lane);
-  }
-  if (bias_row) {
-    wave_colsum16x64<bf16>(vk, red, w, lane);
-    wave_colsum16x64<bf16>(vv, red + NW * 64, w, lane);
-    if (last_to_arrive(arrived, NW, lane)) {
-      wave_sum_out(red, NW, bias_row + p.H * DH + h * DH, lane);
-      wave_sum_out(red + NW * 64, NW, bias_row + 2 * p.H * DH + h * DH, lane);
+  for_halves<NH>([&](auto HF) __attribute__((always_inline)) {
+    constexpr int hf = decltype(HF)::value;
+    float vk[4][4], vv[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        vk[dt][r] = dk[4 * hf + dt][r] * p.scale;
+        vv[dt][r] = DM != 0 ? dv[4 * hf + dt][r] * p.inv_keep : dv[4 * hf + dt][r];
+      }
+    char* dk_dst = p.dk + ((tok0 + k0) * p.dk_ld + h * DHT + 64 * hf) * 2;
+    char* dv_dst = p.dv + ((tok0 + k0) * p.dv_ld + h * DHT + 64 * hf) * 2;
+    if constexpr (RAG) {
+      if (p.rope_k)
+        rope_back_tile_clamped<DHT>(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1, hf);
+      store_tile16x64<bf16>(vk, scr, dk_dst, p.dk_ld, lane, T_ - k0);
+      store_tile16x64<bf16>(vv, scr, dv_dst, p.dv_ld, lane, T_ - k0);
+    } else {
+      if (p.rope_k) rope_back_tile<DHT>(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, hf);
+      store_tile16x64<bf16>(vk, scr, dk_dst, p.dk_ld, lane);
+      store_tile16x64<bf16>(vv, scr, dv_dst, p.dv_ld, lane);
     }
-  }
+    if (bias_row) {
+      wave_colsum16x64<bf16>(vk, red + hf * NW * 64, w, lane);
+      wave_colsum16x64<bf16>(vv, red_v + hf * NW * 64, w, lane);
+      if (hf == NH - 1 && last_to_arrive(arrived, NW, lane)) {
+#pragma unroll
+        for (int h2 = 0; h2 < NH; ++h2) {
+          wave_sum_out(red + h2 * NW * 64, NW, bias_row + p.H * DHT + h * DHT + 64 * h2, lane);
+          wave_sum_out(red_v + h2 * NW * 64, NW, bias_row + 2 * p.H * DHT + h * DHT + 64 * h2, lane);
+        }
+      }
+    }
+  });
 }
 
-template <int DM, bool RAG>
+template <int DHT, int DM, bool RAG>
 int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
-  int rc = launch(attn_bwd_dq_long_kernel<DM, RAG>, grid, DQ_LDS, st, p, "nstl_attn_bwd long dq", LNT);
+  int rc = launch(attn_bwd_dq_long_kernel<DHT, DM, RAG>, grid, DqLds<DHT>::BYTES, st, p, "nstl_attn_bwd long dq", LNT);
   if (rc) return rc;
-  return launch(attn_bwd_dkv_long_kernel<DM, RAG>, grid, dkv_lds_bytes(p.T), st, p, "nstl_attn_bwd long dkv", LNT);
+  return launch(attn_bwd_dkv_long_kernel<DHT, DM, RAG>, grid, dkv_lds_bytes<DHT>(p.T), st, p, "nstl_attn_bwd long dkv",
+                LNT);
 }
-template <int DM>
+template <int DHT, int DM>
 int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
-  return p.T % 32 ? launch_bwd<DM, true>(grid, st, p) : launch_bwd<DM, false>(grid, st, p);
+  return p.T % 32 ? launch_bwd<DHT, DM, true>(grid, st, p) : launch_bwd<DHT, DM, false>(grid, st, p);
+}
+template <int DHT>
+int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
+  if (!p.thresh) return launch_bwd<DHT, 0>(grid, st, p);
+  if (p.mask) return launch_bwd<DHT, 1>(grid, st, p);
+  return launch_bwd<DHT, 2>(grid, st, p);
+}
+template <int DHT>
+int launch_fwd(dim3 grid, hipStream_t st, const AttnParams& p) {
+  constexpr size_t lds = 2 * Geo<DHT>::BUF_B;
+  if (p.T % 32) {
+    if (p.thresh) return launch(attn_fwd_long_kernel<DHT, true, true>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
+    return launch(attn_fwd_long_kernel<DHT, false, true>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
+  }
+  if (p.thresh) return launch(attn_fwd_long_kernel<DHT, true>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
+  return launch(attn_fwd_long_kernel<DHT, false>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
 }
 
 }  // namespace
@@ -608,8 +758,16 @@ namespace nstl {
 bool attn_long_takes(const nstl_attn_args* a) {
   const char* e = getenv("NSTL_ATTN_LONG");
   if (e && e[0] == '0') return false;
-  if (a->dh != DH || a->dtype != NSTL_BF16 || a->T <= 0 || a->T > LONG_MAX_T) return false;
-  if (a->T % 32 == 0) return a->T > LONG_MIN_T;
+  if (a->dtype != NSTL_BF16 || a->T <= 0 || a->T > LONG_MAX_T) return false;
+  if (a->dh == 128) {
+    // head_dim 128 has no one-shot kernels: whole tiles stream at every length, for a
+    // caller that asked for it (without the bit: the generic kernels, as in version 2)
+    if (!(a->flags & NSTL_ATTN_DH128_OK)) return false;
+    if (a->T % 32 == 0) return true;
+  } else {
+    if (a->dh != DH) return false;
+    if (a->T % 32 == 0) return a->T > LONG_MIN_T;
+  }
   // ragged T, any length: only for a caller whose side buffers are sized for it
   e = getenv("NSTL_ATTN_RAGGED");
   return (a->flags & NSTL_ATTN_RAGGED_OK) && !(e && e[0] == '0');
@@ -618,20 +776,13 @@ bool attn_long_takes(const nstl_attn_args* a) {
 int attn_long_fwd(const AttnParams& p, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_FWD_LONG);
   const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
-  if (p.T % 32) {
-    if (p.thresh) return launch(attn_fwd_long_kernel<true, true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
-    return launch(attn_fwd_long_kernel<false, true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
-  }
-  if (p.thresh) return launch(attn_fwd_long_kernel<true>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
-  return launch(attn_fwd_long_kernel<false>, grid, 2 * BUF_B, st, p, "nstl_attn_fwd long", LNT);
+  return p.dh == 128 ? launch_fwd<128>(grid, st, p) : launch_fwd<64>(grid, st, p);
 }
 
 int attn_long_bwd(const AttnParams& p, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_BWD_LONG);
   const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
-  if (!p.thresh) return launch_bwd<0>(grid, st, p);
-  if (p.mask) return launch_bwd<1>(grid, st, p);
-  return launch_bwd<2>(grid, st, p);
+  return p.dh == 128 ? launch_bwd<128>(grid, st, p) : launch_bwd<64>(grid, st, p);
 }
 
 }  // namespace nstl

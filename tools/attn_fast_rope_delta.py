@@ -2,7 +2,7 @@
 from the float64 values of the f32 tables of engine.rotation_tables.
 
 The factors never leave the kernel, so they are read through its outputs: one fast-mode
-streaming backward (bf16, head_dim 64, window T, no dropout) over many heads; the stored
+streaming backward (bf16, head_dim --dh, window T, no dropout) over many heads; the stored
 (even, odd) pairs of dq and dk are R(t, i)^T of the unrotated gradient, which
 tests/attn_ref.py gives in float64.  Per (t, i), over the heads, the pairs whose
 unrotated reference is at least half its row's maximum are solved by least squares for
@@ -12,7 +12,7 @@ and delta(t, i) = max(|cos' - cos|, |sin' - sin|).  The outputs are bf16 and car
 dS rounding, so the solve has a resolution: its standard error is printed beside the
 deviations, which mean something only where they exceed it several times.
 
-  python tools/attn_fast_rope_delta.py [--T 300] [--batches 32] [--out FILE]
+  python tools/attn_fast_rope_delta.py [--T 300] [--batches 32] [--dh 64|128] [--out FILE]
 """
 import argparse
 import os
@@ -26,16 +26,17 @@ from neurosync_trainer_lite_amd import _hip as K  # noqa: E402
 from neurosync_trainer_lite_amd.engine import rotation_tables  # noqa: E402
 from tests import attn_ref as A  # noqa: E402
 
-DEV, DH, HN, STEP = "cuda:0", 64, 16, 4
+DEV, HN, STEP = "cuda:0", 16, 4
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=300)
     ap.add_argument("--batches", type=int, default=32, help="heads = 16 x batches (a multiple of 4)")
+    ap.add_argument("--dh", type=int, default=64, choices=(64, 128), help="head width of the streaming kernels")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    T, Bn = args.T, args.batches
+    T, Bn, DH = args.T, args.batches, args.dh
     assert Bn % STEP == 0
     os.environ["NSTL_ROPE_BWD"] = "fast"
     M, D = Bn * T, HN * DH
@@ -48,7 +49,7 @@ def main():
     dsum = torch.zeros(Bn * HN * T, device=DEV)
     cs, sn = rotation_tables(T, DH, DEV)
     a = K.attn_args(K.BF16, Bn, T, HN, qkv.data_ptr(), 3 * D, qkv[:, D:].data_ptr(), 3 * D, qkv[:, 2 * D:].data_ptr(),
-                    3 * D, o.data_ptr(), D, lse.data_ptr(), 0.0, 0, dh=DH, flags=K.ATTN_RAGGED_OK)
+                    3 * D, o.data_ptr(), D, lse.data_ptr(), 0.0, 0, dh=DH, flags=K.ATTN_RAGGED_OK | K.ATTN_DH128_OK)
     K.kernel_counts_reset()
     K.attn_fwd(a)
     a.dout, a.dout_ld = do.data_ptr(), D
@@ -89,8 +90,8 @@ def main():
     small, large = ok & (ang <= 1.0), ok & (ang > 1.0)
     a_half = delta[small].max().item()
     lines = ["launches %s" % counts,
-             "T=%d heads=%d pairs used per (t, i): min %d median %d (entries with < 8, left out: %d)" % (
-                 T, Bn * HN, int(cnt.min()), int(cnt.median()), int((~ok).sum())),
+             "T=%d head_dim=%d heads=%d pairs used per (t, i): min %d median %d (entries with < 8, left out: %d)" % (
+                 T, DH, Bn * HN, int(cnt.min()), int(cnt.median()), int((~ok).sum())),
              "max delta                          %.3e  (2^-10 = %.3e)" % (delta[ok].max().item(), 2.0 ** -10),
              "A/2: max delta at angle <= 1       %.3e" % a_half,
              "B/2: max (delta - A/2) / angle     %.3e  (angle = t inv_freq_i > 1)" % (

@@ -2,7 +2,11 @@
 q|k|v as slices of one [M, 3D] buffer): fwd and bwd time with dropout 0.3 vs 0
 (the difference is the counter-hash mask cost).  python tools/bench_attn.py
 NSTL_BENCH_T sets the window (B = 128 * 128 // T); a ragged T runs with
-NSTL_ATTN_RAGGED_OK, as the engine sets it (NSTL_BENCH_RAGGED=0: without)."""
+NSTL_ATTN_RAGGED_OK, as the engine sets it (NSTL_BENCH_RAGGED=0: without).
+NSTL_BENCH_DH sets the head width (64 or 128) with H = 1024 // dh, so FLOPs and
+q / k / v / o bytes equal the head_dim 64 case; 128 runs with NSTL_ATTN_DH128_OK, as
+the engine sets it (NSTL_ATTN_LONG=0: the generic kernels, the A/B arm).  The launch
+counters of one forward + backward are printed, so a run names the kernels it timed."""
 import os
 import sys
 
@@ -13,9 +17,10 @@ from neurosync_trainer_lite_amd import _hip as K  # noqa: E402
 from neurosync_trainer_lite_amd.engine import rotation_tables  # noqa: E402
 
 T = int(os.environ.get("NSTL_BENCH_T", "128"))     # 256: BASELINE C5's long clips (B halved)
-B, H, DH = 128 * 128 // T, 16, 64
+DH = int(os.environ.get("NSTL_BENCH_DH", "64"))
+B, H = 128 * 128 // T, 1024 // DH
 D, M = H * DH, B * T
-FLAGS = K.ATTN_RAGGED_OK if os.environ.get("NSTL_BENCH_RAGGED", "1") == "1" else 0
+FLAGS = (K.ATTN_RAGGED_OK if os.environ.get("NSTL_BENCH_RAGGED", "1") == "1" else 0) | K.ATTN_DH128_OK
 dev = "cuda:0"
 bf = torch.bfloat16
 
@@ -47,7 +52,7 @@ if os.environ.get("NSTL_ATTN_MASK", "1") == "1":   # stored keep bits (0: re-has
 for p in [float(x) for x in os.environ.get("NSTL_BENCH_P", "0.3,0.0").split(",")]:
     def args():
         a = K.attn_args(K.BF16, B, T, H, qkv.data_ptr(), 3 * D, qkv[:, D:].data_ptr(), 3 * D,
-                        qkv[:, 2 * D:].data_ptr(), 3 * D, o.data_ptr(), D, lse.data_ptr(), p, 77, flags=FLAGS)
+                        qkv[:, 2 * D:].data_ptr(), 3 * D, o.data_ptr(), D, lse.data_ptr(), p, 77, dh=DH, flags=FLAGS)
         a.dout, a.dout_ld = do.data_ptr(), D
         a.dq, a.dq_ld, a.dk, a.dk_ld, a.dv, a.dv_ld = (dqkv.data_ptr(), 3 * D, dqkv[:, D:].data_ptr(), 3 * D,
                                                         dqkv[:, 2 * D:].data_ptr(), 3 * D)
@@ -63,8 +68,12 @@ for p in [float(x) for x in os.environ.get("NSTL_BENCH_P", "0.3,0.0").split(",")
                 a.dbias_part = extra["part"].data_ptr()
         return a
     a = args()
+    K.kernel_counts_reset()
+    K.attn_fwd(a)
+    K.attn_bwd(a)
+    ran = "+".join(k for k, v in K.kernel_counts().items() if v and k.startswith("attn"))
     tf = t(lambda: K.attn_fwd(a))
     tb = t(lambda: K.attn_bwd(a))
     fl_f, fl_b = 4 * B * H * T * T * DH, 10 * B * H * T * T * DH
-    print("p=%.1f  fwd %7.1f us (%5.1f TF/s)   bwd %7.1f us (%5.1f TF/s)" % (
-        p, tf * 1e6, fl_f / tf / 1e12, tb * 1e6, fl_b / tb / 1e12))
+    print("T=%d dh=%d H=%d p=%.1f  fwd %7.1f us (%5.1f TF/s)   bwd %7.1f us (%5.1f TF/s)  [%s]" % (
+        T, DH, H, p, tf * 1e6, fl_f / tf / 1e12, tb * 1e6, fl_b / tb / 1e12, ran))
