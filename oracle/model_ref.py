@@ -66,8 +66,24 @@ def layer_norm(p, name, x):
     return F.layer_norm(x, (x.shape[-1],), p[name + ".weight"], p[name + ".bias"], LN_EPS)
 
 
-def attention(p, name, xq, xkv, num_heads, attn_dropout=0.0, training=False):
-    """MultiHeadAttention.forward, model.py:110-141 (SDPA path, no mask)."""
+def _drop(t, p_drop, training, masks, where):
+    """One dropout site.  masks=None: F.dropout (torch's RNG).  Otherwise the site's
+    mask is an input: masks[(is_encoder, layer, site)], already keep / (1 - p) and
+    shaped like t (site names: neurosync_trainer_lite_amd/engine.py _SITE)."""
+    if masks is None:
+        return F.dropout(t, p_drop, training)
+    return t * masks[where].to(t.dtype)
+
+
+def _site_kw(masks, is_encoder, layer):
+    """The masks / where keywords of a block call: none without masks, so a caller's
+    stand-in for `attention` or `ffn` with the plain signature keeps working."""
+    return lambda site: {} if masks is None else dict(masks=masks, where=(is_encoder, layer, site))
+
+
+def attention(p, name, xq, xkv, num_heads, attn_dropout=0.0, training=False, masks=None, where=None):
+    """MultiHeadAttention.forward, model.py:110-141 (SDPA path, no mask).
+    masks / where: the probabilities' dropout mask [B, H, Tq, Tk] (see _drop)."""
     B, Tq, D = xq.shape
     Tk = xkv.shape[1]
     dh = D // num_heads
@@ -78,37 +94,43 @@ def attention(p, name, xq, xkv, num_heads, attn_dropout=0.0, training=False):
     k = head_rope(k)
     s = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(dh)
     a = torch.softmax(s, dim=-1)
-    if training and attn_dropout > 0:
+    if masks is not None:
+        a = _drop(a, attn_dropout, training, masks, where)
+    elif training and attn_dropout > 0:
         a = F.dropout(a, attn_dropout, True)
     o = torch.matmul(a, v).transpose(1, 2).reshape(B, Tq, D)
     return linear(p, name + ".out_linear", o)
 
 
-def ffn(p, name, x, dropout=0.0, training=False):
-    """FeedForwardNetwork.forward, model.py:153-158."""
+def ffn(p, name, x, dropout=0.0, training=False, masks=None, where=None):
+    """FeedForwardNetwork.forward, model.py:153-158.
+    masks / where: the hidden's dropout mask [B, T, 4D] (see _drop)."""
     h = F.relu(linear(p, name + ".linear1", x))
-    h = F.dropout(h, dropout, training)
+    h = _drop(h, dropout, training, masks, where)
     return linear(p, name + ".linear2", h)
 
 
-def encoder_layer(p, name, x, num_heads, dropout=0.0, training=False):
-    """CustomTransformerEncoderLayer.forward (post-LN), model.py:173-181."""
-    d = lambda t: F.dropout(t, dropout, training)
-    a = d(attention(p, name + ".self_attn", x, x, num_heads, dropout, training))
-    x = layer_norm(p, name + ".norm1", x + d(a))
-    f = ffn(p, name + ".ffn", x, dropout, training)
-    return layer_norm(p, name + ".norm2", x + d(f))
+def encoder_layer(p, name, x, num_heads, dropout=0.0, training=False, masks=None, layer=0):
+    """CustomTransformerEncoderLayer.forward (post-LN), model.py:173-181.
+    masks: injected dropout masks of the whole model, `layer` this layer's index in them."""
+    d = lambda t, site: _drop(t, dropout, training, masks, (True, layer, site))
+    m = _site_kw(masks, True, layer)
+    a = d(attention(p, name + ".self_attn", x, x, num_heads, dropout, training, **m("attn")), "drop1")
+    x = layer_norm(p, name + ".norm1", x + d(a, "resid"))
+    f = ffn(p, name + ".ffn", x, dropout, training, **m("ffn"))
+    return layer_norm(p, name + ".norm2", x + d(f, "drop2"))
 
 
-def decoder_layer(p, name, x, mem, num_heads, dropout=0.0, training=False):
+def decoder_layer(p, name, x, mem, num_heads, dropout=0.0, training=False, masks=None, layer=0):
     """CustomTransformerDecoderLayer.forward (post-LN), model.py:196-208."""
-    d = lambda t: F.dropout(t, dropout, training)
-    a = d(attention(p, name + ".self_attn", x, x, num_heads, dropout, training))
-    x = layer_norm(p, name + ".norm1", x + d(a))
-    c = d(attention(p, name + ".multihead_attn", x, mem, num_heads, dropout, training))
-    x = layer_norm(p, name + ".norm2", x + d(c))
-    f = ffn(p, name + ".ffn", x, dropout, training)
-    return layer_norm(p, name + ".norm3", x + d(f))
+    d = lambda t, site: _drop(t, dropout, training, masks, (False, layer, site))
+    m = _site_kw(masks, False, layer)
+    a = d(attention(p, name + ".self_attn", x, x, num_heads, dropout, training, **m("attn")), "drop1")
+    x = layer_norm(p, name + ".norm1", x + d(a, "resid"))
+    c = d(attention(p, name + ".multihead_attn", x, mem, num_heads, dropout, training, **m("xattn")), "drop2x")
+    x = layer_norm(p, name + ".norm2", x + d(c, "xresid"))
+    f = ffn(p, name + ".ffn", x, dropout, training, **m("ffn"))
+    return layer_norm(p, name + ".norm3", x + d(f, "drop3"))
 
 
 def n_layers_of(p):
@@ -118,27 +140,28 @@ def n_layers_of(p):
     return n
 
 
-def encoder_forward(p, src, num_heads, dropout=0.0, training=False):
+def encoder_forward(p, src, num_heads, dropout=0.0, training=False, masks=None):
     """Encoder.forward, model.py:223-230."""
     x = global_pe(linear(p, "encoder.embedding", src))
     for i in range(n_layers_of(p)):
-        x = encoder_layer(p, "encoder.transformer_encoder.%d" % i, x, num_heads, dropout, training)
+        x = encoder_layer(p, "encoder.transformer_encoder.%d" % i, x, num_heads, dropout, training, masks, i)
     return layer_norm(p, "encoder.layer_norm", x)
 
 
-def decoder_forward(p, mem, num_heads, dropout=0.0, training=False):
+def decoder_forward(p, mem, num_heads, dropout=0.0, training=False, masks=None):
     """Decoder.forward, model.py:245-251 (memory = un-rotated encoder output)."""
     x = global_pe(mem)
     for i in range(n_layers_of(p)):
-        x = decoder_layer(p, "decoder.transformer_decoder.%d" % i, x, mem, num_heads, dropout, training)
+        x = decoder_layer(p, "decoder.transformer_decoder.%d" % i, x, mem, num_heads, dropout, training, masks, i)
     x = layer_norm(p, "decoder.layer_norm", x)
     return linear(p, "decoder.fc_output", x)
 
 
-def seq2seq_forward(p, src, num_heads, dropout=0.0, training=False):
-    """Seq2Seq.forward, model.py:263-266."""
-    return decoder_forward(p, encoder_forward(p, src, num_heads, dropout, training),
-                           num_heads, dropout, training)
+def seq2seq_forward(p, src, num_heads, dropout=0.0, training=False, masks=None):
+    """Seq2Seq.forward, model.py:263-266.  masks: {(is_encoder, layer, site): keep / (1 - p)}
+    replaces every F.dropout draw (see _drop); None keeps torch's RNG."""
+    return decoder_forward(p, encoder_forward(p, src, num_heads, dropout, training, masks),
+                           num_heads, dropout, training, masks)
 
 
 # ----------------------------------------------------------------------------
@@ -207,10 +230,13 @@ class OracleTrainer:
         self.v = [torch.zeros_like(self.p[k]) for k in self.keys]
         self.step_count = 0
 
-    def step(self, src, trg):
+    def step(self, src, trg, masks=None):
+        """masks: this step's injected dropout masks (seq2seq_forward); they change with
+        every forward's seed, so they belong to the call."""
         for k in self.keys:
             self.p[k].grad = None
-        pred = seq2seq_forward(self.p, src, self.num_heads, self.dropout, self.dropout > 0)
+        pred = seq2seq_forward(self.p, src, self.num_heads, self.dropout, self.dropout > 0 or masks is not None,
+                               masks)
         loss = loss_fn(pred, trg, *self.loss_args)
         loss.backward()
         grads = [self.p[k].grad for k in self.keys]
