@@ -306,10 +306,12 @@ class FusedAdam(torch.optim.Optimizer):
             for p in self.param_groups[0]["params"]:
                 self.state[p]["step"] = torch.tensor(float(self._nstl_step))
         sd = super().state_dict()
-        for s in sd["state"].values():
-            for k, v in list(s.items()):
-                if torch.is_tensor(v) and k != "step":
-                    s[k] = v.clone()
+        # torch packs self.state's own per-parameter dicts: the copies go into new
+        # dicts, so that self.state keeps its views of the moment arenas (a clone
+        # written back would detach it, and every later state_dict() would return
+        # the moments as of this call)
+        sd["state"] = {i: {k: v.clone() if torch.is_tensor(v) and k != "step" else v for k, v in s.items()}
+                       for i, s in sd["state"].items()}
         return sd
 
     def load_state_dict(self, state_dict):

@@ -17,6 +17,10 @@ Differences in mechanism, not in meaning:
     (parallel.GradAllReducer).  The reference's single-process list of replicas
     (training_utils.py:131-303) is also accepted: gradients are averaged into
     models[0]'s arena and parameters copied back, as it does.
+
+train_one_epoch's mode (update overlapped with the next forward, clip norm from the
+backward's partials, validation forwards under a queued update, a smaller last
+batch) is covered by tests/test_epoch_life_gpu.py.
 """
 import math
 import os
