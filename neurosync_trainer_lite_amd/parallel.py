@@ -607,32 +607,47 @@ class ShardPusher(GradAllReducer):
     failed = False
     check = None
 
-    def verify(self, g_full, g_shard, partial, sumsq_fn, rtol=1e-4):
+    def verify(self, g_full, g_shard, partial, sumsq_fn):
         """g_shard (own slice + the pushed slots, nstl_shard_sum) against the
         reduce-scatter of the same gradient arena, once (the first step): the
         copies cross devices only on a multi-GPU node, so this is where per-step
         ordering of pushes, sync and owner reads is checked on the hardware.
-        The sums add the same f32 terms in another order, so they agree to
-        rounding (|diff| <= rtol * max|sum|); a lost or stale slice is off by a
-        whole contribution.  The ranks agree on the outcome; on a mismatch this
-        step continues with the reduce-scatter's shard (and partial sums of
-        squares) and self.failed is set: the step's caller then runs zero1.
-        Returns whether the pushed sums were right (on every rank)."""
+        The check is per element.  Both sums add the same `world` f32 terms
+        g_r, in different orders; a recursive f32 sum of n terms is within
+        (n - 1) u sum|g_r| of the exact one (u = 2^-24, to first order), so two
+        of them differ by at most 2 (n - 1) u sum_r |g_r|: the gate is
+        n 2^-23 A per element, A = the reduce-scatter of |g| (one more
+        reduction on this step; its own rounding, a factor 1 + (n - 1) u, fits
+        in the n against n - 1).  The bound follows sum|g_r|, not |sum g_r|, so
+        cancelling contributions pass, while a lost or stale slice is off by a
+        whole contribution wherever that contribution is above ~1e-6 of the
+        element's sum|g_r|, however small next to the rest of the shard.  The
+        ranks agree on the outcome; on a mismatch this step continues with the
+        reduce-scatter's shard (and partial sums of squares) and self.failed
+        is set: the step's caller then runs zero1.  Returns whether the pushed
+        sums were right (on every rank)."""
         self.verify_pending = False
-        ref = torch.empty_like(g_shard)
-        self.comm.reduce_scatter(g_full[:self.comm.numel], ref)
-        diff = float((g_shard - ref).abs().max())
-        scale = float(ref.abs().max())
-        ok_here = diff <= rtol * scale
-        flag = torch.tensor([1.0 if ok_here else 0.0], device=g_shard.device)
+        n = self.comm.numel
+        ref, mag = torch.empty_like(g_shard), torch.empty_like(g_shard)
+        self.comm.reduce_scatter(g_full[:n], ref)
+        self.comm.reduce_scatter(g_full[:n].abs(), mag)
+        err = (g_shard - ref).abs()
+        bound = mag * (self.world * 2.0 ** -23)
+        n_bad = int((~(err <= bound)).sum())  # a NaN on either side counts as wrong
+        at = int((err - bound).argmax())
+        diff, scale = float(err.max()), float(ref.abs().max())
+        flag = torch.tensor([1.0 if n_bad == 0 else 0.0], device=g_shard.device)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
         ok = flag.item() >= 1.0
-        self.check = {"max_abs_diff": diff, "max_abs": scale, "rtol": rtol, "ok": ok,
+        self.check = {"max_abs_diff": diff, "max_abs": scale, "elements_over": n_bad,
+                      "worst": {"at": self.comm.lo + at, "abs_diff": float(err[at]), "bound": float(bound[at])},
+                      "bound": "per element: world * 2^-23 * sum over ranks of |g|", "ok": ok,
                       "what": "first step: pushed shard sums vs reduce-scatter of the same arena"}
         if not ok:
             import sys
-            print("NSTL_DP=zero1_push: pushed shard sums differ from the reduce-scatter (rank %d: max |diff| %.3g of "
-                  "max %.3g); this step uses the reduce-scatter, later steps run zero1" % (self.comm.rank, diff, scale),
+            print("NSTL_DP=zero1_push: pushed shard sums differ from the reduce-scatter (rank %d: %d elements over "
+                  "their rounding bound, max |diff| %.3g of max %.3g); this step uses the reduce-scatter, later steps "
+                  "run zero1" % (self.comm.rank, n_bad, diff, scale),
                   file=sys.stderr)
             g_shard.copy_(ref)
             sumsq_fn(g_shard, partial)

@@ -157,7 +157,15 @@ class FusedAdam(torch.optim.Optimizer):
             if max_norm is not None:
                 K.sumsq(grads, grads.numel(), partial, N_PARTIAL, stream=st)
 
-        if self._comm is None and self.overlap_next_forward and self._overlap_allowed and closure is None:
+        # replicated beside a reducer (NSTL_DP=allreduce): the overlapped update reads
+        # the arena as it is, so it runs only over gradients an in-backward
+        # all-reduce finished (consumed here); any others (written by hand, or a
+        # backward that raised) take the in-order branch, which reduces them first
+        red = eng.grad_reducer if self._comm is None else None
+        exchanged = red is None or not red.active or red.completed
+        if self._comm is None and self.overlap_next_forward and self._overlap_allowed and closure is None and exchanged:
+            if red is not None and red.active:
+                red.consume()
             # clip coefficient on the current stream, the update in arena ranges on
             # the side stream (nstl_adam_step reads the coefficient: no LDS, so its
             # workgroups fit beside the forward's ring-GEMM workgroups)

@@ -21,6 +21,9 @@ Differences in mechanism, not in meaning:
 train_one_epoch's mode (update overlapped with the next forward, clip norm from the
 backward's partials, validation forwards under a queued update, a smaller last
 batch) is covered by tests/test_epoch_life_gpu.py.
+train_one_epoch_multi_gpu under torch.distributed (attach_data_parallel in every NSTL_DP
+mode at 2 and 3 ranks, rank_batches' leftovers, rank 0's validation between sharded steps,
+consolidate / checkpoint / resume) is covered by tests/test_dist_epoch_gpu.py.
 """
 import math
 import os

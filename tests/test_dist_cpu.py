@@ -364,14 +364,22 @@ def _push_verify_worker(rank, port, out_dir, world, corrupt):
     ns = 64 * 840
     comm = parallel.ShardComm(ns)
     grads = torch.randn(ns, generator=torch.Generator().manual_seed(10 + rank))
+    quiet = slice(100, 1100)  # of rank 0's shard: every rank's gradients there are ~1e-7 of the shard's largest
+    if corrupt == "small":
+        grads[quiet] *= 1e-7
     red = parallel.ShardPusher.create(grads, comm, bucket_bytes=4000)
     red.begin(True)
     red.ready(ns)
     red.finish()
     assert red.consume()
     slots = red.slots()
-    if corrupt and rank == 0:
+    if corrupt is True and rank == 0:
         slots[0, 17] += 1.0  # one stale element in one slot of one rank
+    if corrupt == "small" and rank == 0:
+        # one sender's slice lost where every |gradient| is far below 1e-4 x max|sum| of the
+        # shard (the whole-shard gate this check had): each element is off by a whole contribution
+        assert float(grads[quiet].abs().max()) < 1e-2 * 1e-4 * float(grads[comm.lo:comm.hi].abs().max())
+        slots[0, quiet] = 0.0
     gs, part = torch.empty(comm.shard), torch.zeros(4)
 
     def sumsq_fn(x, p):
@@ -393,16 +401,20 @@ def _push_verify_worker(rank, port, out_dir, world, corrupt):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,corrupt", [(2, False), (4, False), (4, True)])
+@pytest.mark.parametrize("world,corrupt", [(2, False), (4, False), (4, True), (8, False), (4, "small"), (2, "small")])
 def test_push_first_step_verified_against_reduce_scatter_gloo(tmp_path, world, corrupt):
     """the first step's pushed shard sums (own + slots) are checked
     against the reduce-scatter of the same arena, on every rank, and the ranks
     agree: one stale element on one rank fails the check everywhere; that step
     then continues on the reduce-scatter's shard and sums of squares, and the
-    reducer is marked failed (the optimizer runs zero1 from then on)."""
+    reducer is marked failed (the optimizer runs zero1 from then on).
+    ADVICE r6 #2, "small": the check is per element against the f32 rounding of a
+    world-term sum, so a lost slice fails it even where every gradient of the
+    slice is a ten-millionth of the shard's largest."""
     mp.spawn(_push_verify_worker, args=(_port(), str(tmp_path), world, corrupt), nprocs=world, join=True)
     for r in range(world):
         out = torch.load(tmp_path / ("v%d.pt" % r), weights_only=True)
+        corrupt = bool(corrupt)
         assert out["ok"] == out["check"] == (not corrupt), out
         assert out["failed"] == corrupt and out["pending"] is False
         assert out["gs_ok"] and out["part_ok"], out

@@ -446,7 +446,7 @@ def test_update_overlapped_with_next_forward_is_identical(amp, trust):
         cfg, model, crit, opt, _ = make(D, H, L, 31, amp=amp, dropout=0.1)
         model.train()
         opt.overlap_next_forward = overlap
-        opt._overlap_allowed = True  # the path is opt-in (NSTL_ADAM_OVERLAP=1)
+        opt._overlap_allowed = True  # allowed by default; NSTL_ADAM_OVERLAP=0 in the environment must not turn this test off
         opt.trust_backward_norm = trust  # the clip norm from the dW epilogues' partials (bench.py, train_one_epoch)
         g = torch.Generator().manual_seed(5)
         losses, norms = [], []
