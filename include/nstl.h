@@ -144,10 +144,13 @@ int nstl_fp8_quant_cols(int x_dtype, const nstl_fp8_job* jobs, int n, void* stre
  *                   (T % 32 != 0, 1 <= T <= 4096; NSTL_ATTN_RAGGED=0: off).
  *                   With NSTL_ATTN_DH128_OK in flags also dh == 128, bf16, at every
  *                   1 <= T <= 4096 (there are no one-shot kernels at that width;
- *                   ragged T needs both flags; NSTL_ATTN_LONG=0: off);
+ *                   ragged T needs both flags; NSTL_ATTN_LONG=0: off).
+ *                   With NSTL_ATTN_DHANY_OK in flags also every other dh % 8 == 0,
+ *                   8 <= dh < 128, bf16, on the same terms as dh == 128 (dh == 64
+ *                   and dh == 128 do not read this bit);
  *   generic       : everything else with dh % 8 == 0, dh <= 512, T <= 4096 (f32
- *                   past T = 128, other head sizes, dh == 128 or ragged T without
- *                   their flags):
+ *                   past T = 128, head sizes above 128, dh != 64 or ragged T
+ *                   without their flags):
  *                   one wave per row, no MFMA; a correctness path, not a
  *                   training path. */
 #define NSTL_ATTN_RAGGED_OK 1u /* flags bit 0: mask_bits / dbias_part are sized by nstl_attn_mask_words /
@@ -156,6 +159,8 @@ int nstl_fp8_quant_cols(int x_dtype, const nstl_fp8_job* jobs, int n, void* stre
 #define NSTL_ATTN_DH128_OK 2u /* flags bit 1: a bf16 call with dh == 128 may take the streaming MFMA kernels; the
                                  caller sizes mask_bits / dbias_part by nstl_attn_mask_words / nstl_attn_bias_rows
                                  (both 0 without the bit: the generic kernels, which ignore them) */
+#define NSTL_ATTN_DHANY_OK 4u /* flags bit 2: the same for a bf16 call with dh % 8 == 0, 8 <= dh < 128, dh != 64
+                                 (dh == 64 and dh == 128 do not read it; 128 keeps its own bit) */
 typedef struct nstl_attn_args {
   int dtype;
   int B, T, H, dh;
@@ -175,8 +180,9 @@ typedef struct nstl_attn_args {
   uint64_t* mask_bits;        /* optional [B*H*T*T/64] ([nstl_attn_mask_words()] with
                                  NSTL_ATTN_RAGGED_OK): the dropout keep bits.  Forward
                                  writes them, backward reads them instead of re-hashing
-                                 (MFMA paths: head_dim 64, and 128 with
-                                 NSTL_ATTN_DH128_OK; ignored elsewhere).  NULL:
+                                 (MFMA paths: head_dim 64, 128 with
+                                 NSTL_ATTN_DH128_OK, the other widths up to 128 with
+                                 NSTL_ATTN_DHANY_OK; ignored elsewhere).  NULL:
                                  both directions hash (seed, element). */
   float* dbias_part;          /* optional backward output [nstl_attn_bias_rows()][3*H*dh] f32:
                                  per-(batch, 128-row block) column sums of dq | dk | dv as
@@ -379,7 +385,9 @@ const char* nstl_last_error_string(void);
 /* ABI version: raised whenever a struct of this header changes size or layout, or
    a flag is added.
    2: nstl_attn_args.flags, nstl_attn_mask_words.
-   3: NSTL_ATTN_DH128_OK (streaming MFMA attention at head_dim 128). */
+   3: NSTL_ATTN_DH128_OK (streaming MFMA attention at head_dim 128).
+   4: NSTL_ATTN_DHANY_OK (streaming MFMA attention at every head_dim % 8 == 0 up to
+      128); no struct changed. */
 int nstl_version(void);
 
 /* Launch counters by kernel family, process-wide (host side, counted at each
@@ -405,7 +413,8 @@ enum {
   NSTL_K_GEMM_FP8_ROPE,      /* fp8 GEMM launches with the RoPE epilogue (C5 q|k|v, cross q, cross k|v) */
   NSTL_K_GEMM4F8,            /* fp8 GEMM launches on the 4-wave persistent kernel (the rest: NSTL_K_GEMM_FP8) */
   NSTL_K_ATTN_FWD_LONG,      /* streaming MFMA attention forward (bf16; head_dim 64: 256 < T <= 4096 and
-                                ragged T; head_dim 128 with NSTL_ATTN_DH128_OK: every T) */
+                                ragged T; head_dim 128 with NSTL_ATTN_DH128_OK, other widths up to 128
+                                with NSTL_ATTN_DHANY_OK: every T) */
   NSTL_K_ATTN_BWD_LONG,      /*   ... its backward (dQ + dK/dV kernel pair) */
   NSTL_K_COUNT
 };

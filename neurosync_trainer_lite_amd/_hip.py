@@ -70,6 +70,7 @@ class AttnArgs(ctypes.Structure):
 
 ATTN_RAGGED_OK = 1  # NSTL_ATTN_RAGGED_OK
 ATTN_DH128_OK = 2   # NSTL_ATTN_DH128_OK
+ATTN_DHANY_OK = 4   # NSTL_ATTN_DHANY_OK
 
 
 class LnArgs(ctypes.Structure):
@@ -453,8 +454,10 @@ def transpose_bf16(jobs, stream=None):
 def attn_args(dtype, B, T, H, q, q_ld, k, k_ld, v, v_ld, o, o_ld, lse, p_drop, seed, dh=64, flags=0):
     """`flags`: ATTN_RAGGED_OK lets a ragged T (T % 32 != 0) take the streaming MFMA
     kernels, ATTN_DH128_OK lets a bf16 call with dh = 128 take them (at every T; a
-    ragged T needs both); mask_bits / dbias_part are then sized by attn_mask_words /
-    attn_bias_rows.  Without them dh = 128 and ragged T run the generic kernels."""
+    ragged T needs both), ATTN_DHANY_OK the same for every other dh % 8 == 0 below 128
+    (dh = 64 and 128 do not read it); mask_bits / dbias_part are then sized by
+    attn_mask_words / attn_bias_rows.  Without them dh != 64 and ragged T run the
+    generic kernels."""
     a = AttnArgs()
     a.flags = flags
     a.dtype = dtype

@@ -1295,7 +1295,7 @@ int fill(AttnParams& p, const nstl_attn_args* a, bool bwd) {
     NSTL_CHECK_ARG(!(a->rope_q || a->rope_k) || (a->rope_cos && a->rope_sin), "nstl_attn_bwd: rope tables");
     const bool mfma = use_fast(a) || nstl::attn_long_takes(a);
     NSTL_CHECK_ARG(!mfma || a->dsum, "nstl_attn_bwd: dsum scratch [B*H*T] f32 missing");
-    NSTL_CHECK_ARG(!a->dbias_part || mfma, "nstl_attn_bwd: dbias_part needs an MFMA path (head_dim 64, or 128 with its flag)");
+    NSTL_CHECK_ARG(!a->dbias_part || mfma, "nstl_attn_bwd: dbias_part needs an MFMA path (head_dim 64, or another width up to 128 with its flag)");
   }
   p.q = (const char*)a->q; p.q_ld = a->q_ld;
   p.k = (const char*)a->k; p.k_ld = a->k_ld;

@@ -343,4 +343,79 @@ NSTL_DEV void wave_sum_out(const float* red, int nw, float* out, int lane) {
   out[lane] = cs;
 }
 
+// ---------------------------------------------------------------------------
+// The epilogue helpers for a head of RUNTIME width (the streaming kernels' head
+// widths other than 64 and 128: any multiple of 8).  A result tile is still 16 x 64
+// in registers and in the staging image; ncols = min(64, dh - 64 hf) of its columns
+// exist.  Nothing is stored to, summed into or read from (RoPE tables) a column at or
+// past ncols: those belong to the next head, the next operand or nobody.
+//
+// store_tile16x64 with a column limit as well: 16-byte chunks at or past ncols (a
+// multiple of 8) and rows >= nrows are staged but not stored.
+template <typename T>
+NSTL_DEV void store_tile16xw(const float (&v)[4][4], char* scr, char* gbase, int64_t ld_elems, int lane, int nrows,
+                             int ncols) {
+  constexpr int ESZ = (int)sizeof(T), RB = DH * ESZ, CPR = RB / 16;
+  const int g = lane >> 4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) *(T*)(scr + (4 * g + r) * RB + (dt * 16 + (lane & 15)) * ESZ) = from_f32<T>(v[dt][r]);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int c = lane; c < 16 * CPR; c += 64) {
+    const int row = c / CPR, ch = c % CPR;
+    if (row < nrows && ch * (16 / ESZ) < ncols)
+      *(uint4*)(gbase + (int64_t)row * ld_elems * ESZ + ch * 16) = *(const uint4*)(scr + row * RB + ch * 16);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+// rope_tab_clamped for tables of row stride dh / 2: the pair index is clamped to the
+// head's last pair, so a lane whose column is absent reads (and then rotates garbage
+// by) an angle inside its own table row; its result is never stored
+NSTL_DEV void rope_tab_w(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, const float* cs, const float* sn,
+                         int row_last, int i0, int dh) {
+  const int rs = dh >> 1;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const int i = min(row0 + r, row_last) * rs + min(i0 + dt * 8 + (c >> 1), rs - 1);
+      tc[dt][r] = cs[i];
+      ts[dt][r] = (c & 1) ? -sn[i] : sn[i];
+    }
+}
+// rope_tab_fast with the head width (the divisor of the frequency exponent) at run time
+NSTL_DEV void rope_tab_fast_w(float (&tc)[4][4], float (&ts)[4][4], int row0, int c, int i0, int dh) {
+  const float sgn_rev = ((c & 1) ? -1.f : 1.f) * 0.15915494309189535f;  // +-1/(2pi)
+  const float fdh = (float)dh;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    const float two_i = (float)(2 * (i0 + dt * 8 + (c >> 1)));
+    const float inv_freq = __expf(-9.21034049987793f * two_i / fdh);  // f32(ln 10000)
+    const float f = inv_freq * sgn_rev;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float a = (float)(row0 + r) * f;
+      ts[dt][r] = __builtin_amdgcn_sinf(a);
+      tc[dt][r] = __builtin_amdgcn_cosf(a);
+    }
+  }
+}
+// rope_back_tile_clamped for columns 64 hf .. of a dh-wide head (pairs are adjacent
+// columns, so a pair is wholly present or wholly absent)
+NSTL_DEV void rope_back_tile_w(float (&v)[4][4], int row0, int c, const float* cs, const float* sn, bool fast,
+                               int row_last, int hf, int dh) {
+  float tc[4][4], ts[4][4];
+  if (fast) rope_tab_fast_w(tc, ts, row0, c, 32 * hf, dh);
+  else rope_tab_w(tc, ts, row0, c, cs, sn, row_last, 32 * hf, dh);
+  rope_apply(v, tc, ts);
+}
+// wave_sum_out for the first ncols columns only
+NSTL_DEV void wave_sum_out_w(const float* red, int nw, float* out, int lane, int ncols) {
+  float cs = 0.f;
+  for (int k = 0; k < nw; ++k) cs += red[k * 64 + lane];
+  if (lane < ncols) out[lane] = cs;
+}
+
 }  // namespace

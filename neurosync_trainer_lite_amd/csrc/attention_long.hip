@@ -14,6 +14,18 @@
 // rotated (RoPE^T pair index 32 half + ...) and column-summed one half at a time.  The
 // <64, ...> instantiations are the kernels as they were before DHT.
 //
+// Every other width dh % 8 == 0 below 128 (a caller that sets NSTL_ATTN_DHANY_OK) runs
+// the ANY instantiations: DHT is then the image class (64: dh <= 56 in one image, 128:
+// 72 <= dh <= 120 in two) and the width is p.dh.  Columns at and past dh are absent:
+// their DMA pieces are fetched from piece 0 of the same head's row (TileDmaW), the
+// wave's own-row fragments are exact zeros there (row_frag_w), nothing is stored,
+// summed or looked up (RoPE tables) for them (attention_dev.h: store_tile16xw,
+// wave_sum_out_w, rope_tab_w).  HI (compile time) says whether the upper 32 columns of
+// the last image hold anything; without it that k-chunk and its two accumulator tiles
+// are not compiled in.  It is not a run-time branch because the inline-asm LDS reads
+// must reach their lgkm_fence() in straight-line code: a read in a conditional block
+// had its result register moved at the merge, before the data had landed.
+//
 // Here nothing of size T x T or T per lane is held.  Every kernel owns a block of
 // 128 rows of one (batch, head) -- 8 waves, 16 rows each, the wave's own rows
 // loaded from global memory straight into MFMA fragments -- and walks the other
@@ -120,6 +132,58 @@ NSTL_DEV TileDma<DHT> tile_dma(const char* a, int64_t a_ld, const char* b, int64
   d.T = T;
   return d;
 }
+// The same for a head of runtime width dh (a multiple of 8, 64 (NH - 1) < dh < 64 NH):
+// the lane's 16-byte source piece of image hf is columns 64 hf + 8 lc .. + 7, and a
+// piece at or past dh is fetched from piece 0 of the same row of the same head
+// instead -- no byte outside row * ld + h * dh + [0, dh) is read, and the absent
+// columns of an image hold finite data (a copy of columns 0 .. 7).
+template <int DHT> struct TileDmaW {
+  static constexpr int NH = Geo<DHT>::NH, OP_B = Geo<DHT>::OP_B, BUF_B = Geo<DHT>::BUF_B;
+  const char* a; int64_t a_ldb;
+  const char* b; int64_t b_ldb;
+  int lrow, T, off[NH];  // off[hf]: byte offset of the lane's piece in the head's row
+  NSTL_DEV void issue(char* smem, int t, int buf, int w) const {
+    const int row = min(t * KT + lrow, T - 1);
+#pragma unroll
+    for (int hf = 0; hf < NH; ++hf) dma1k(a + row * a_ldb + off[hf], smem + buf * BUF_B + hf * TILE_B + w * 1024);
+#pragma unroll
+    for (int hf = 0; hf < NH; ++hf)
+      dma1k(b + row * b_ldb + off[hf], smem + buf * BUF_B + OP_B + hf * TILE_B + w * 1024);
+  }
+};
+template <int DHT>
+NSTL_DEV TileDmaW<DHT> tile_dma_w(const char* a, int64_t a_ld, const char* b, int64_t b_ld, int64_t tok0, int h, int dh,
+                                  int T, int w, int lane) {
+  TileDmaW<DHT> d;
+  d.a = a + (tok0 * a_ld + h * dh) * 2; d.a_ldb = a_ld * 2;
+  d.b = b + (tok0 * b_ld + h * dh) * 2; d.b_ldb = b_ld * 2;
+  d.lrow = w * 8 + (lane >> 3);
+  const int lc = (lane & 7) ^ att_x(d.lrow);
+#pragma unroll
+  for (int hf = 0; hf < Geo<DHT>::NH; ++hf) d.off[hf] = 64 * hf + 8 * lc < dh ? (64 * hf + 8 * lc) * 2 : 0;
+  d.T = T;
+  return d;
+}
+// ANY selects the runtime-width form of a kernel's operand stream and head width
+template <int DHT, bool ANY> struct DmaSel { using type = TileDma<DHT>; };
+template <int DHT> struct DmaSel<DHT, true> { using type = TileDmaW<DHT>; };
+template <int DHT, bool ANY>
+NSTL_DEV typename DmaSel<DHT, ANY>::type tile_dma_sel(const char* a, int64_t a_ld, const char* b, int64_t b_ld,
+                                                      int64_t tok0, int h, int dh, int T, int w, int lane) {
+  if constexpr (ANY) return tile_dma_w<DHT>(a, a_ld, b, b_ld, tok0, h, dh, T, w, lane);
+  else return tile_dma<DHT>(a, a_ld, b, b_ld, tok0, h, T, w, lane);
+}
+template <int DHT, bool ANY>
+NSTL_DEV int head_width(const AttnParams& p) {
+  if constexpr (ANY) return p.dh;
+  else return DHT;
+}
+// own-row fragment u of a head of runtime width dh: elements 32 u + 8 g .. + 7 of the
+// row, an exact zero (and no read) where that piece is at or past dh
+NSTL_DEV bf16x8 row_frag_w(const bf16* row, int u, int g, int dh) {
+  bf16x8 z = {};
+  return 32 * u + 8 * g < dh ? *(const bf16x8*)(row + 32 * u + 8 * g) : z;
+}
 
 // ---------------------------------------------------------------------------
 // Forward.  s[kt][r] = score(query q0 + c, key 64 t + 16 kt + 4g + r): a lane holds
@@ -127,9 +191,11 @@ NSTL_DEV TileDma<DHT> tile_dma(const char* a, int64_t a_ld, const char* b, int64
 // permlane swaps for the tile maximum).  The running sum stays a per-lane partial
 // (the four lanes of a query rescale by the same factor) and is reduced once at
 // the end.  LDS: 2 x (K | V) = 32 KB (head_dim 64) / 64 KB (128).
-template <int DHT, bool DROP, bool RAG = false>
+template <int DHT, bool DROP, bool RAG = false, bool ANY = false, bool HI = true>
 __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_fwd_long_kernel(AttnParams p) {
   constexpr int NH = Geo<DHT>::NH, OP_B = Geo<DHT>::OP_B, BUF_B = Geo<DHT>::BUF_B;
+  static_assert((!ANY || RAG) && (ANY || HI), "the runtime-width kernels are the ragged ones");
+  const int dh = head_width<DHT, ANY>(p);  // ANY: 64 (NH - 1) < dh < 64 NH, dh % 8 == 0
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
@@ -138,7 +204,7 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_fwd_long_kernel(AttnP
   const int64_t tok0 = (int64_t)b * T_;
   const int q0 = blockIdx.x * ROWS + w * 16;
   const bool act = q0 < T_;
-  const TileDma<DHT> dma = tile_dma<DHT>(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
+  const auto dma = tile_dma_sel<DHT, ANY>(p.k, p.k_ld, p.v, p.v_ld, tok0, h, dh, T_, w, lane);
   dma.issue(smem, 0, 0, w);
   // RAG: a wave that straddles T reads its rows past the head from row T - 1 and
   // stores nothing for them
@@ -146,10 +212,17 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_fwd_long_kernel(AttnP
   const bool qok = !RAG || q0 + c < T_;
   bf16x8 fq[2 * NH] = {};  // elements 32 u + 8g .. + 7 of the query's row, u = 0 .. 2 NH - 1
   if (act) {
-    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DHT;
+    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * dh;
 #pragma unroll
-    for (int u = 0; u < 2 * NH; ++u) fq[u] = *(const bf16x8*)(qrow + 32 * u + 8 * g);
+    for (int u = 0; u < 2 * NH; ++u) {
+      if constexpr (ANY) fq[u] = row_frag_w(qrow, u, g, dh);
+      else fq[u] = *(const bf16x8*)(qrow + 32 * u + 8 * g);
+    }
   }
+  // ANY: 32-column k-chunks 0 .. 2 NH - 2 hold at least one present piece, the last one
+  // only if dh > DHT - 32, which is HI; with it go accumulator tiles 2 and 3 of the last
+  // half.  Without HI their LDS reads and MFMAs are not compiled in.
+  constexpr bool last_kc = !ANY || HI;
   const float c2 = p.scale * LOG2E;
   float m = -INFINITY, lsum = 0.f;
   f32x4 o[4 * NH];
@@ -172,7 +245,8 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_fwd_long_kernel(AttnP
       for (int hf = 0; hf < NH; ++hf)
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-          asm_row128(fk[4 * hf + u], Kimg + hf * TILE_B, (kt + (u >> 1)) * 16 + c, 32 * (u & 1) + 8 * g);
+          if (!ANY || 2 * hf + (u & 1) < 2 * NH - 1 || last_kc)
+            asm_row128(fk[4 * hf + u], Kimg + hf * TILE_B, (kt + (u >> 1)) * 16 + c, 32 * (u & 1) + 8 * g);
       lgkm_fence();
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -180,7 +254,7 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_fwd_long_kernel(AttnP
 #pragma unroll
         for (int hf = 0; hf < NH; ++hf) {
           mma16(s[kt + u], fk[4 * hf + 2 * u], fq[2 * hf]);
-          mma16(s[kt + u], fk[4 * hf + 2 * u + 1], fq[2 * hf + 1]);
+          if (!ANY || hf < NH - 1 || last_kc) mma16(s[kt + u], fk[4 * hf + 2 * u + 1], fq[2 * hf + 1]);
         }
       }
     }
@@ -276,10 +350,12 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_fwd_long_kernel(AttnP
       for (int hf = 0; hf < NH; ++hf) {
         bf16x8 fv[4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) asm_col2_128(fv[dt], Vimg + hf * TILE_B, dt * 16, 32 * j, lane);
+        for (int dt = 0; dt < 4; ++dt)
+          if (hf < NH - 1 || dt < 2 || last_kc) asm_col2_128(fv[dt], Vimg + hf * TILE_B, dt * 16, 32 * j, lane);
         lgkm_fence();
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) mma16(o[4 * hf + dt], fv[dt], fp);
+        for (int dt = 0; dt < 4; ++dt)
+          if (hf < NH - 1 || dt < 2 || last_kc) mma16(o[4 * hf + dt], fv[dt], fp);
       }
     }
   }
@@ -288,11 +364,13 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_fwd_long_kernel(AttnP
   sum = sum_xor32(sum);
   const float inv = (DROP ? p.inv_keep : 1.f) * __builtin_amdgcn_rcpf(sum);
   if (!qok) return;
-  bf16* orow = (bf16*)p.o + (tok0 + q0 + c) * p.o_ld + h * DHT + 4 * g;
+  bf16* orow = (bf16*)p.o + (tok0 + q0 + c) * p.o_ld + h * dh + 4 * g;
 #pragma unroll
   for (int dt = 0; dt < 4 * NH; ++dt) {
     const f32x4 x = o[dt] * inv;
-    *(bf16x4*)(orow + 16 * dt) = (bf16x4){(bf16)x[0], (bf16)x[1], (bf16)x[2], (bf16)x[3]};
+    // ANY: dh % 8 == 0, so the lane's four columns 16 dt + 4g .. + 3 are all present or all absent
+    if (!ANY || 16 * dt + 4 * g < dh)
+      *(bf16x4*)(orow + 16 * dt) = (bf16x4){(bf16)x[0], (bf16)x[1], (bf16)x[2], (bf16)x[3]};
   }
   if (g == 0) p.lse[(int64_t)bh * T_ + q0 + c] = m * p.scale + logf(sum);
 }
@@ -307,9 +385,12 @@ template <int DHT> struct DqLds {
   static constexpr size_t BYTES = ARR_OFF + 16;
 };
 
-template <int DHT, int DM, bool RAG = false>
+template <int DHT, int DM, bool RAG = false, bool ANY = false, bool HI = true>
 __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(AttnParams p) {
   constexpr int NH = Geo<DHT>::NH, OP_B = Geo<DHT>::OP_B, BUF_B = Geo<DHT>::BUF_B;
+  static_assert((!ANY || RAG) && (ANY || HI), "the runtime-width kernels are the ragged ones");
+  const int dh = head_width<DHT, ANY>(p);  // ANY: 64 (NH - 1) < dh < 64 NH, dh % 8 == 0
+  constexpr bool last_kc = !ANY || HI;  // the last 32-column k-chunk (accumulator tiles 2, 3 of the last half) exists
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* red = (float*)(smem + DqLds<DHT>::RED_OFF);  // [NH][NW][64]
   unsigned* arrived = (unsigned*)(smem + DqLds<DHT>::ARR_OFF);
@@ -320,7 +401,7 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(At
   const int64_t tok0 = (int64_t)b * T_;
   const int q0 = blockIdx.x * ROWS + w * 16;
   const bool act = q0 < T_;
-  const TileDma<DHT> dma = tile_dma<DHT>(p.k, p.k_ld, p.v, p.v_ld, tok0, h, T_, w, lane);
+  const auto dma = tile_dma_sel<DHT, ANY>(p.k, p.k_ld, p.v, p.v_ld, tok0, h, dh, T_, w, lane);
   dma.issue(smem, 0, 0, w);
   // stored keep bits of this wave's 16 queries against tile t: lane kt * 4 + r holds word (kt, r)
   auto load_mask = [&](int t) -> uint64_t {
@@ -336,15 +417,21 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(At
   const int qr = RAG ? min(q0 + c, T_ - 1) : q0 + c;
   const bool qok = !RAG || q0 + c < T_;
   if (act) {
-    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * DHT;
-    const bf16* drow = (const bf16*)p.dout + (tok0 + qr) * p.dout_ld + h * DHT;
-    const bf16* orow = (const bf16*)p.o + (tok0 + qr) * p.o_ld + h * DHT;
+    const bf16* qrow = (const bf16*)p.q + (tok0 + qr) * p.q_ld + h * dh;
+    const bf16* drow = (const bf16*)p.dout + (tok0 + qr) * p.dout_ld + h * dh;
+    const bf16* orow = (const bf16*)p.o + (tok0 + qr) * p.o_ld + h * dh;
     bf16x8 oo[2 * NH];
 #pragma unroll
     for (int u = 0; u < 2 * NH; ++u) {
-      fq[u] = *(const bf16x8*)(qrow + 32 * u + 8 * g);
-      fo[u] = *(const bf16x8*)(drow + 32 * u + 8 * g);
-      oo[u] = *(const bf16x8*)(orow + 32 * u + 8 * g);
+      if constexpr (ANY) {  // pieces at or past dh: exact zeros, nothing read
+        fq[u] = row_frag_w(qrow, u, g, dh);
+        fo[u] = row_frag_w(drow, u, g, dh);
+        oo[u] = row_frag_w(orow, u, g, dh);
+      } else {
+        fq[u] = *(const bf16x8*)(qrow + 32 * u + 8 * g);
+        fo[u] = *(const bf16x8*)(drow + 32 * u + 8 * g);
+        oo[u] = *(const bf16x8*)(orow + 32 * u + 8 * g);
+      }
     }
     float dpart = 0.f;
 #pragma unroll
@@ -383,14 +470,14 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(At
         for (int u = 0; u < 2; ++u) {
           const int row = (2 * j + u) * 16 + c;
           asm_row128(fb[4 * u + 0], Kimg, row, 8 * g);
-          asm_row128(fb[4 * u + 1], Kimg, row, 32 + 8 * g);
+          if (NH == 2 || last_kc) asm_row128(fb[4 * u + 1], Kimg, row, 32 + 8 * g);
           asm_row128(fb[4 * u + 2], Vimg, row, 8 * g);
-          asm_row128(fb[4 * u + 3], Vimg, row, 32 + 8 * g);
+          if (NH == 2 || last_kc) asm_row128(fb[4 * u + 3], Vimg, row, 32 + 8 * g);
           if constexpr (NH == 2) {
             asm_row128(fb[8 + 4 * u + 0], Kimg + TILE_B, row, 8 * g);
-            asm_row128(fb[8 + 4 * u + 1], Kimg + TILE_B, row, 32 + 8 * g);
+            if (last_kc) asm_row128(fb[8 + 4 * u + 1], Kimg + TILE_B, row, 32 + 8 * g);
             asm_row128(fb[8 + 4 * u + 2], Vimg + TILE_B, row, 8 * g);
-            asm_row128(fb[8 + 4 * u + 3], Vimg + TILE_B, row, 32 + 8 * g);
+            if (last_kc) asm_row128(fb[8 + 4 * u + 3], Vimg + TILE_B, row, 32 + 8 * g);
           }
         }
         lgkm_fence();
@@ -400,16 +487,16 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(At
           const int ktl = 2 * j + u, kt = t * (KT / 16) + ktl;
           f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
           mma16(sc, fb[4 * u + 0], fq[0]);
-          mma16(sc, fb[4 * u + 1], fq[1]);
+          if (NH == 2 || last_kc) mma16(sc, fb[4 * u + 1], fq[1]);
           if constexpr (NH == 2) {
             mma16(sc, fb[8 + 4 * u + 0], fq[2]);
-            mma16(sc, fb[8 + 4 * u + 1], fq[3]);
+            if (last_kc) mma16(sc, fb[8 + 4 * u + 1], fq[3]);
           }
           mma16(dp, fb[4 * u + 2], fo[0]);
-          mma16(dp, fb[4 * u + 3], fo[1]);
+          if (NH == 2 || last_kc) mma16(dp, fb[4 * u + 3], fo[1]);
           if constexpr (NH == 2) {
             mma16(dp, fb[8 + 4 * u + 2], fo[2]);
-            mma16(dp, fb[8 + 4 * u + 3], fo[3]);
+            if (last_kc) mma16(dp, fb[8 + 4 * u + 3], fo[3]);
           }
           // sc[r] / dp[r]: S^T / dP^T at (key 16 kt + 4g + r, query q0 + c)
           bool keep[4] = {true, true, true, true};
@@ -438,30 +525,37 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(At
         const bf16x8 fa = acc_frag<bf16>(dsv[0], dsv[1]);  // dS, row = query q0 + c
         bf16x8 fc[4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) asm_col2_128(fc[dt], Kimg, dt * 16, 32 * j, lane);
+        for (int dt = 0; dt < 4; ++dt)
+          if (NH == 2 || dt < 2 || last_kc) asm_col2_128(fc[dt], Kimg, dt * 16, 32 * j, lane);
         lgkm_fence();
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) mma16(dq[dt], fa, fc[dt]);
+        for (int dt = 0; dt < 4; ++dt)
+          if (NH == 2 || dt < 2 || last_kc) mma16(dq[dt], fa, fc[dt]);
         if constexpr (NH == 2) {  // columns 64 .. 127
 #pragma unroll
-          for (int dt = 0; dt < 4; ++dt) asm_col2_128(fc[dt], Kimg + TILE_B, dt * 16, 32 * j, lane);
+          for (int dt = 0; dt < 4; ++dt)
+            if (dt < 2 || last_kc) asm_col2_128(fc[dt], Kimg + TILE_B, dt * 16, 32 * j, lane);
           lgkm_fence();
 #pragma unroll
-          for (int dt = 0; dt < 4; ++dt) mma16(dq[4 + dt], fa, fc[dt]);
+          for (int dt = 0; dt < 4; ++dt)
+            if (dt < 2 || last_kc) mma16(dq[4 + dt], fa, fc[dt]);
         }
       }
     }
     mcur = mnext;
   }
   __syncthreads();  // every wave is done with the tiles: the buffers become output staging
-  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * DHT : nullptr;
+  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * dh : nullptr;
   if (!act) {
     if (bias_row) {
 #pragma unroll
       for (int hf = 0; hf < NH; ++hf) red[hf * NW * 64 + w * 64 + lane] = 0.f;
       if (last_to_arrive(arrived, NW, lane)) {
 #pragma unroll
-        for (int hf = 0; hf < NH; ++hf) wave_sum_out(red + hf * NW * 64, NW, bias_row + h * DHT + 64 * hf, lane);
+        for (int hf = 0; hf < NH; ++hf) {
+          if constexpr (ANY) wave_sum_out_w(red + hf * NW * 64, NW, bias_row + h * dh + 64 * hf, lane, dh - 64 * hf);
+          else wave_sum_out(red + hf * NW * 64, NW, bias_row + h * DHT + 64 * hf, lane);
+        }
       }
     }
     return;
@@ -474,8 +568,11 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(At
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) vq[dt][r] = dq[4 * hf + dt][r] * p.scale;
-    char* dq_dst = p.dq + ((tok0 + q0) * p.dq_ld + h * DHT + 64 * hf) * 2;
-    if constexpr (RAG) {
+    char* dq_dst = p.dq + ((tok0 + q0) * p.dq_ld + h * dh + 64 * hf) * 2;
+    if constexpr (ANY) {  // dh - 64 hf columns of this half exist: tables, stores and sums stop there
+      if (p.rope_q) rope_back_tile_w(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1, hf, dh);
+      store_tile16xw<bf16>(vq, smem + w * 2048, dq_dst, p.dq_ld, lane, T_ - q0, dh - 64 * hf);
+    } else if constexpr (RAG) {
       if (p.rope_q)
         rope_back_tile_clamped<DHT>(vq, q0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1, hf);
       store_tile16x64<bf16>(vq, smem + w * 2048, dq_dst, p.dq_ld, lane, T_ - q0);
@@ -487,7 +584,10 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(At
       wave_colsum16x64<bf16>(vq, red + hf * NW * 64, w, lane);
       if (hf == NH - 1 && last_to_arrive(arrived, NW, lane)) {
 #pragma unroll
-        for (int h2 = 0; h2 < NH; ++h2) wave_sum_out(red + h2 * NW * 64, NW, bias_row + h * DHT + 64 * h2, lane);
+        for (int h2 = 0; h2 < NH; ++h2) {
+          if constexpr (ANY) wave_sum_out_w(red + h2 * NW * 64, NW, bias_row + h * dh + 64 * h2, lane, dh - 64 * h2);
+          else wave_sum_out(red + h2 * NW * 64, NW, bias_row + h * DHT + 64 * h2, lane);
+        }
       }
     }
   });
@@ -508,9 +608,12 @@ template <int DHT> size_t dkv_lds_bytes(int T) {
   return (size_t)2 * Geo<DHT>::BUF_B + (size_t)2 * dkv_rows(T) * 4 + 2 * Geo<DHT>::NH * NW * 64 * 4 + 16;
 }
 
-template <int DHT, int DM, bool RAG = false>
+template <int DHT, int DM, bool RAG = false, bool ANY = false, bool HI = true>
 __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   constexpr int NH = Geo<DHT>::NH, OP_B = Geo<DHT>::OP_B, BUF_B = Geo<DHT>::BUF_B;
+  static_assert((!ANY || RAG) && (ANY || HI), "the runtime-width kernels are the ragged ones");
+  const int dh = head_width<DHT, ANY>(p);  // ANY: 64 (NH - 1) < dh < 64 NH, dh % 8 == 0
+  constexpr bool last_kc = !ANY || HI;  // the last 32-column k-chunk (accumulator tiles 2, 3 of the last half) exists
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
   const int Tp = RAG ? ntile * KT : T_;  // dkv_rows(T)
@@ -524,7 +627,7 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   const int64_t tok0 = (int64_t)b * T_;
   const int k0 = blockIdx.x * ROWS + w * 16;
   const bool act = k0 < T_;
-  const TileDma<DHT> dma = tile_dma<DHT>(p.q, p.q_ld, p.dout, p.dout_ld, tok0, h, T_, w, lane);
+  const auto dma = tile_dma_sel<DHT, ANY>(p.q, p.q_ld, p.dout, p.dout_ld, tok0, h, dh, T_, w, lane);
   dma.issue(smem, 0, 0, w);
   if constexpr (RAG) {  // queries past T: P = 2^(s - inf) = 0 and dS = 0 * (dP - 0) = 0
     for (int i = tid; i < Tp; i += LNT) {
@@ -550,12 +653,17 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   const int kr = RAG ? min(k0 + c, T_ - 1) : k0 + c;
   const bool kok = !RAG || k0 + c < T_;
   if (act) {
-    const bf16* krow = (const bf16*)p.k + (tok0 + kr) * p.k_ld + h * DHT;
-    const bf16* vrow = (const bf16*)p.v + (tok0 + kr) * p.v_ld + h * DHT;
+    const bf16* krow = (const bf16*)p.k + (tok0 + kr) * p.k_ld + h * dh;
+    const bf16* vrow = (const bf16*)p.v + (tok0 + kr) * p.v_ld + h * dh;
 #pragma unroll
     for (int u = 0; u < 2 * NH; ++u) {
-      fk[u] = *(const bf16x8*)(krow + 32 * u + 8 * g);
-      fv[u] = *(const bf16x8*)(vrow + 32 * u + 8 * g);
+      if constexpr (ANY) {  // pieces at or past dh: exact zeros, nothing read
+        fk[u] = row_frag_w(krow, u, g, dh);
+        fv[u] = row_frag_w(vrow, u, g, dh);
+      } else {
+        fk[u] = *(const bf16x8*)(krow + 32 * u + 8 * g);
+        fv[u] = *(const bf16x8*)(vrow + 32 * u + 8 * g);
+      }
     }
     if (DM == 1) mcur = load_mask(0);
   }
@@ -585,14 +693,14 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
         for (int u = 0; u < 2; ++u) {
           const int row = (2 * j + u) * 16 + c;
           asm_row128(fb[4 * u + 0], Qimg, row, 8 * g);
-          asm_row128(fb[4 * u + 1], Qimg, row, 32 + 8 * g);
+          if (NH == 2 || last_kc) asm_row128(fb[4 * u + 1], Qimg, row, 32 + 8 * g);
           asm_row128(fb[4 * u + 2], Dimg, row, 8 * g);
-          asm_row128(fb[4 * u + 3], Dimg, row, 32 + 8 * g);
+          if (NH == 2 || last_kc) asm_row128(fb[4 * u + 3], Dimg, row, 32 + 8 * g);
           if constexpr (NH == 2) {
             asm_row128(fb[8 + 4 * u + 0], Qimg + TILE_B, row, 8 * g);
-            asm_row128(fb[8 + 4 * u + 1], Qimg + TILE_B, row, 32 + 8 * g);
+            if (last_kc) asm_row128(fb[8 + 4 * u + 1], Qimg + TILE_B, row, 32 + 8 * g);
             asm_row128(fb[8 + 4 * u + 2], Dimg + TILE_B, row, 8 * g);
-            asm_row128(fb[8 + 4 * u + 3], Dimg + TILE_B, row, 32 + 8 * g);
+            if (last_kc) asm_row128(fb[8 + 4 * u + 3], Dimg + TILE_B, row, 32 + 8 * g);
           }
           const int qb = t * KT + (2 * j + u) * 16 + 4 * g;  // this lane's four queries
           l4[u] = asm_f32x4(lse_s + qb);
@@ -605,16 +713,16 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
           const int qtl = 2 * j + u;
           f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = {0.f, 0.f, 0.f, 0.f};
           mma16(st, fb[4 * u + 0], fk[0]);
-          mma16(st, fb[4 * u + 1], fk[1]);
+          if (NH == 2 || last_kc) mma16(st, fb[4 * u + 1], fk[1]);
           if constexpr (NH == 2) {
             mma16(st, fb[8 + 4 * u + 0], fk[2]);
-            mma16(st, fb[8 + 4 * u + 1], fk[3]);
+            if (last_kc) mma16(st, fb[8 + 4 * u + 1], fk[3]);
           }
           mma16(dpt, fb[4 * u + 2], fv[0]);
-          mma16(dpt, fb[4 * u + 3], fv[1]);
+          if (NH == 2 || last_kc) mma16(dpt, fb[4 * u + 3], fv[1]);
           if constexpr (NH == 2) {
             mma16(dpt, fb[8 + 4 * u + 2], fv[2]);
-            mma16(dpt, fb[8 + 4 * u + 3], fv[3]);
+            if (last_kc) mma16(dpt, fb[8 + 4 * u + 3], fv[3]);
           }
           // keep bits of (queries 4g + r, key k0 + c): 4 consecutive bits of word (qtl, key % 4)
           uint32_t nib = 0;
@@ -639,26 +747,34 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
         bf16x8 fc[8];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          asm_col2_128(fc[2 * dt], Dimg, dt * 16, 32 * j, lane);
-          asm_col2_128(fc[2 * dt + 1], Qimg, dt * 16, 32 * j, lane);
+          if (NH == 2 || dt < 2 || last_kc) {
+            asm_col2_128(fc[2 * dt], Dimg, dt * 16, 32 * j, lane);
+            asm_col2_128(fc[2 * dt + 1], Qimg, dt * 16, 32 * j, lane);
+          }
         }
         lgkm_fence();
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          mma16(dv[dt], fa1, fc[2 * dt]);
-          mma16(dk[dt], fa2, fc[2 * dt + 1]);
+          if (NH == 2 || dt < 2 || last_kc) {
+            mma16(dv[dt], fa1, fc[2 * dt]);
+            mma16(dk[dt], fa2, fc[2 * dt + 1]);
+          }
         }
         if constexpr (NH == 2) {  // columns 64 .. 127
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) {
-            asm_col2_128(fc[2 * dt], Dimg + TILE_B, dt * 16, 32 * j, lane);
-            asm_col2_128(fc[2 * dt + 1], Qimg + TILE_B, dt * 16, 32 * j, lane);
+            if (dt < 2 || last_kc) {
+              asm_col2_128(fc[2 * dt], Dimg + TILE_B, dt * 16, 32 * j, lane);
+              asm_col2_128(fc[2 * dt + 1], Qimg + TILE_B, dt * 16, 32 * j, lane);
+            }
           }
           lgkm_fence();
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) {
-            mma16(dv[4 + dt], fa1, fc[2 * dt]);
-            mma16(dk[4 + dt], fa2, fc[2 * dt + 1]);
+            if (dt < 2 || last_kc) {
+              mma16(dv[4 + dt], fa1, fc[2 * dt]);
+              mma16(dk[4 + dt], fa2, fc[2 * dt + 1]);
+            }
           }
         }
       }
@@ -666,7 +782,7 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
     mcur = mnext;
   }
   __syncthreads();  // every wave is done with the tiles: the buffers become output staging
-  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * DHT : nullptr;
+  float* bias_row = p.dbias ? p.dbias + (int64_t)(b * gridDim.x + blockIdx.x) * 3 * p.H * dh : nullptr;
   float* red_v = red + NH * NW * 64;
   if (!act) {
     if (bias_row) {
@@ -678,8 +794,13 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
       if (last_to_arrive(arrived, NW, lane)) {
 #pragma unroll
         for (int hf = 0; hf < NH; ++hf) {
-          wave_sum_out(red + hf * NW * 64, NW, bias_row + p.H * DHT + h * DHT + 64 * hf, lane);
-          wave_sum_out(red_v + hf * NW * 64, NW, bias_row + 2 * p.H * DHT + h * DHT + 64 * hf, lane);
+          if constexpr (ANY) {
+            wave_sum_out_w(red + hf * NW * 64, NW, bias_row + p.H * dh + h * dh + 64 * hf, lane, dh - 64 * hf);
+            wave_sum_out_w(red_v + hf * NW * 64, NW, bias_row + 2 * p.H * dh + h * dh + 64 * hf, lane, dh - 64 * hf);
+          } else {
+            wave_sum_out(red + hf * NW * 64, NW, bias_row + p.H * DHT + h * DHT + 64 * hf, lane);
+            wave_sum_out(red_v + hf * NW * 64, NW, bias_row + 2 * p.H * DHT + h * DHT + 64 * hf, lane);
+          }
         }
       }
     }
@@ -697,9 +818,13 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
         vk[dt][r] = dk[4 * hf + dt][r] * p.scale;
         vv[dt][r] = DM != 0 ? dv[4 * hf + dt][r] * p.inv_keep : dv[4 * hf + dt][r];
       }
-    char* dk_dst = p.dk + ((tok0 + k0) * p.dk_ld + h * DHT + 64 * hf) * 2;
-    char* dv_dst = p.dv + ((tok0 + k0) * p.dv_ld + h * DHT + 64 * hf) * 2;
-    if constexpr (RAG) {
+    char* dk_dst = p.dk + ((tok0 + k0) * p.dk_ld + h * dh + 64 * hf) * 2;
+    char* dv_dst = p.dv + ((tok0 + k0) * p.dv_ld + h * dh + 64 * hf) * 2;
+    if constexpr (ANY) {  // dh - 64 hf columns of this half exist: tables, stores and sums stop there
+      if (p.rope_k) rope_back_tile_w(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1, hf, dh);
+      store_tile16xw<bf16>(vk, scr, dk_dst, p.dk_ld, lane, T_ - k0, dh - 64 * hf);
+      store_tile16xw<bf16>(vv, scr, dv_dst, p.dv_ld, lane, T_ - k0, dh - 64 * hf);
+    } else if constexpr (RAG) {
       if (p.rope_k)
         rope_back_tile_clamped<DHT>(vk, k0 + 4 * g, c, p.rope_cos, p.rope_sin, p.rope_fast, T_ - 1, hf);
       store_tile16x64<bf16>(vk, scr, dk_dst, p.dk_ld, lane, T_ - k0);
@@ -715,8 +840,13 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
       if (hf == NH - 1 && last_to_arrive(arrived, NW, lane)) {
 #pragma unroll
         for (int h2 = 0; h2 < NH; ++h2) {
-          wave_sum_out(red + h2 * NW * 64, NW, bias_row + p.H * DHT + h * DHT + 64 * h2, lane);
-          wave_sum_out(red_v + h2 * NW * 64, NW, bias_row + 2 * p.H * DHT + h * DHT + 64 * h2, lane);
+          if constexpr (ANY) {
+            wave_sum_out_w(red + h2 * NW * 64, NW, bias_row + p.H * dh + h * dh + 64 * h2, lane, dh - 64 * h2);
+            wave_sum_out_w(red_v + h2 * NW * 64, NW, bias_row + 2 * p.H * dh + h * dh + 64 * h2, lane, dh - 64 * h2);
+          } else {
+            wave_sum_out(red + h2 * NW * 64, NW, bias_row + p.H * DHT + h * DHT + 64 * h2, lane);
+            wave_sum_out(red_v + h2 * NW * 64, NW, bias_row + 2 * p.H * DHT + h * DHT + 64 * h2, lane);
+          }
         }
       }
     }
@@ -739,6 +869,42 @@ int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
   if (!p.thresh) return launch_bwd<DHT, 0>(grid, st, p);
   if (p.mask) return launch_bwd<DHT, 1>(grid, st, p);
   return launch_bwd<DHT, 2>(grid, st, p);
+}
+// Head widths other than 64 and 128 (8 <= dh < 128, dh % 8 == 0): DHT is the image
+// class (64: one image, 128: two), HI whether the last image's upper 32 columns hold
+// anything, the width itself is p.dh.  One instantiation per class, half and dropout
+// mode serves every T: the ragged form, which at T % 32 == 0 only pads the dK / dV
+// kernel's LSE / D rows to whole tiles (dkv_rows_any).
+int dkv_rows_any(int T) { return (T + KT - 1) / KT * KT; }
+template <int DHT> size_t dkv_lds_bytes_any(int T) {
+  return (size_t)2 * Geo<DHT>::BUF_B + (size_t)2 * dkv_rows_any(T) * 4 + 2 * Geo<DHT>::NH * NW * 64 * 4 + 16;
+}
+template <int DHT, int DM, bool HI>
+int launch_bwd_any(dim3 grid, hipStream_t st, const AttnParams& p) {
+  int rc = launch(attn_bwd_dq_long_kernel<DHT, DM, true, true, HI>, grid, DqLds<DHT>::BYTES, st, p,
+                  "nstl_attn_bwd long dq", LNT);
+  if (rc) return rc;
+  return launch(attn_bwd_dkv_long_kernel<DHT, DM, true, true, HI>, grid, dkv_lds_bytes_any<DHT>(p.T), st, p,
+                "nstl_attn_bwd long dkv", LNT);
+}
+template <int DHT, bool HI>
+int launch_bwd_any(dim3 grid, hipStream_t st, const AttnParams& p) {
+  if (!p.thresh) return launch_bwd_any<DHT, 0, HI>(grid, st, p);
+  if (p.mask) return launch_bwd_any<DHT, 1, HI>(grid, st, p);
+  return launch_bwd_any<DHT, 2, HI>(grid, st, p);
+}
+template <int DHT, bool HI>
+int launch_fwd_any(dim3 grid, hipStream_t st, const AttnParams& p) {
+  constexpr size_t lds = 2 * Geo<DHT>::BUF_B;
+  if (p.thresh)
+    return launch(attn_fwd_long_kernel<DHT, true, true, true, HI>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
+  return launch(attn_fwd_long_kernel<DHT, false, true, true, HI>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
+}
+// image class and half of a runtime width: 8..32 <64, lo>, 40..56 <64, hi>, 72..96 <128, lo>, 104..120 <128, hi>
+template <typename F64L, typename F64H, typename F128L, typename F128H>
+int by_width(int dh, F64L f64l, F64H f64h, F128L f128l, F128H f128h) {
+  if (dh < 64) return dh > 32 ? f64h() : f64l();
+  return dh > 96 ? f128h() : f128l();
 }
 template <int DHT>
 int launch_fwd(dim3 grid, hipStream_t st, const AttnParams& p) {
@@ -764,9 +930,12 @@ bool attn_long_takes(const nstl_attn_args* a) {
     // caller that asked for it (without the bit: the generic kernels, as in version 2)
     if (!(a->flags & NSTL_ATTN_DH128_OK)) return false;
     if (a->T % 32 == 0) return true;
-  } else {
-    if (a->dh != DH) return false;
+  } else if (a->dh == DH) {
     if (a->T % 32 == 0) return a->T > LONG_MIN_T;
+  } else {
+    // every other width up to 128 (fill() has checked dh % 8 == 0): the same, behind a bit of its own
+    if (a->dh <= 0 || a->dh % 8 || a->dh > 128 || !(a->flags & NSTL_ATTN_DHANY_OK)) return false;
+    if (a->T % 32 == 0) return true;
   }
   // ragged T, any length: only for a caller whose side buffers are sized for it
   e = getenv("NSTL_ATTN_RAGGED");
@@ -776,12 +945,20 @@ bool attn_long_takes(const nstl_attn_args* a) {
 int attn_long_fwd(const AttnParams& p, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_FWD_LONG);
   const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
+  if (p.dh != 64 && p.dh != 128)
+    return by_width(
+        p.dh, [&] { return launch_fwd_any<64, false>(grid, st, p); }, [&] { return launch_fwd_any<64, true>(grid, st, p); },
+        [&] { return launch_fwd_any<128, false>(grid, st, p); }, [&] { return launch_fwd_any<128, true>(grid, st, p); });
   return p.dh == 128 ? launch_fwd<128>(grid, st, p) : launch_fwd<64>(grid, st, p);
 }
 
 int attn_long_bwd(const AttnParams& p, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_BWD_LONG);
   const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
+  if (p.dh != 64 && p.dh != 128)
+    return by_width(
+        p.dh, [&] { return launch_bwd_any<64, false>(grid, st, p); }, [&] { return launch_bwd_any<64, true>(grid, st, p); },
+        [&] { return launch_bwd_any<128, false>(grid, st, p); }, [&] { return launch_bwd_any<128, true>(grid, st, p); });
   return p.dh == 128 ? launch_bwd<128>(grid, st, p) : launch_bwd<64>(grid, st, p);
 }
 

@@ -886,7 +886,7 @@ class Seq2SeqEngine:
 
     def _attn(self, q, k, v, o, lse, seed, T, B, mask=None):
         a = K.attn_args(K.dtype_code(self.dt), B, T, self.H, 0, 0, 0, 0, 0, 0, 0, 0, 0, self.p, seed, dh=self.dh,
-                        flags=K.ATTN_RAGGED_OK | K.ATTN_DH128_OK)
+                        flags=K.ATTN_RAGGED_OK | K.ATTN_DH128_OK | K.ATTN_DHANY_OK)
         K.attn_set(a, q=q, k=k, v=v, o=o, lse=lse, mask_bits=mask)
         K.attn_fwd(a, stream=self.st)
 
@@ -896,7 +896,7 @@ class Seq2SeqEngine:
         column sums.  Returns False when the call took the generic kernels (no
         sums: the caller's colsum provides them)."""
         a = K.attn_args(K.dtype_code(self.dt), B, T, self.H, 0, 0, 0, 0, 0, 0, 0, 0, 0, self.p, seed, dh=self.dh,
-                        flags=K.ATTN_RAGGED_OK | K.ATTN_DH128_OK)
+                        flags=K.ATTN_RAGGED_OK | K.ATTN_DH128_OK | K.ATTN_DHANY_OK)
         cs, sn = self.rope(T, self.dh)
         a.rope_q, a.rope_k = 1, 1
         K.attn_set(a, q=q, k=k, v=v, o=o, lse=lse, dout=do, dq=dq, dk=dk, dv=dv, rope_cos=cs, rope_sin=sn,

@@ -12,7 +12,7 @@ and delta(t, i) = max(|cos' - cos|, |sin' - sin|).  The outputs are bf16 and car
 dS rounding, so the solve has a resolution: its standard error is printed beside the
 deviations, which mean something only where they exceed it several times.
 
-  python tools/attn_fast_rope_delta.py [--T 300] [--batches 32] [--dh 64|128] [--out FILE]
+  python tools/attn_fast_rope_delta.py [--T 300] [--batches 32] [--dh 8..128] [--out FILE]
 """
 import argparse
 import os
@@ -33,7 +33,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=300)
     ap.add_argument("--batches", type=int, default=32, help="heads = 16 x batches (a multiple of 4)")
-    ap.add_argument("--dh", type=int, default=64, choices=(64, 128), help="head width of the streaming kernels")
+    ap.add_argument("--dh", type=int, default=64, choices=tuple(range(8, 129, 8)),
+                    help="head width of the streaming kernels (a multiple of 8 up to 128)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     T, Bn, DH = args.T, args.batches, args.dh
@@ -49,7 +50,7 @@ def main():
     dsum = torch.zeros(Bn * HN * T, device=DEV)
     cs, sn = rotation_tables(T, DH, DEV)
     a = K.attn_args(K.BF16, Bn, T, HN, qkv.data_ptr(), 3 * D, qkv[:, D:].data_ptr(), 3 * D, qkv[:, 2 * D:].data_ptr(),
-                    3 * D, o.data_ptr(), D, lse.data_ptr(), 0.0, 0, dh=DH, flags=K.ATTN_RAGGED_OK | K.ATTN_DH128_OK)
+                    3 * D, o.data_ptr(), D, lse.data_ptr(), 0.0, 0, dh=DH, flags=K.ATTN_RAGGED_OK | K.ATTN_DH128_OK | K.ATTN_DHANY_OK)
     K.kernel_counts_reset()
     K.attn_fwd(a)
     a.dout, a.dout_ld = do.data_ptr(), D

@@ -3,10 +3,12 @@ q|k|v as slices of one [M, 3D] buffer): fwd and bwd time with dropout 0.3 vs 0
 (the difference is the counter-hash mask cost).  python tools/bench_attn.py
 NSTL_BENCH_T sets the window (B = 128 * 128 // T); a ragged T runs with
 NSTL_ATTN_RAGGED_OK, as the engine sets it (NSTL_BENCH_RAGGED=0: without).
-NSTL_BENCH_DH sets the head width (64 or 128) with H = 1024 // dh, so FLOPs and
-q / k / v / o bytes equal the head_dim 64 case; 128 runs with NSTL_ATTN_DH128_OK, as
-the engine sets it (NSTL_ATTN_LONG=0: the generic kernels, the A/B arm).  The launch
-counters of one forward + backward are printed, so a run names the kernels it timed."""
+NSTL_BENCH_DH sets the head width (a multiple of 8) with H = 1024 // dh where that
+divides (FLOPs and q / k / v / o bytes then equal the head_dim 64 case), else H = 16
+(dh 96: D = 1536); NSTL_BENCH_H overrides.  128 runs with NSTL_ATTN_DH128_OK and the
+other widths with NSTL_ATTN_DHANY_OK, as the engine sets them (NSTL_ATTN_LONG=0: the
+generic kernels, the A/B arm).  TF/s are at the call's own FLOPs.  The launch counters
+of one forward + backward are printed, so a run names the kernels it timed."""
 import os
 import sys
 
@@ -18,9 +20,10 @@ from neurosync_trainer_lite_amd.engine import rotation_tables  # noqa: E402
 
 T = int(os.environ.get("NSTL_BENCH_T", "128"))     # 256: BASELINE C5's long clips (B halved)
 DH = int(os.environ.get("NSTL_BENCH_DH", "64"))
-B, H = 128 * 128 // T, 1024 // DH
+B = 128 * 128 // T
+H = int(os.environ.get("NSTL_BENCH_H", str(1024 // DH if 1024 % DH == 0 else 16)))
 D, M = H * DH, B * T
-FLAGS = (K.ATTN_RAGGED_OK if os.environ.get("NSTL_BENCH_RAGGED", "1") == "1" else 0) | K.ATTN_DH128_OK
+FLAGS = (K.ATTN_RAGGED_OK if os.environ.get("NSTL_BENCH_RAGGED", "1") == "1" else 0) | K.ATTN_DH128_OK | K.ATTN_DHANY_OK
 dev = "cuda:0"
 bf = torch.bfloat16
 
