@@ -134,33 +134,36 @@ int nstl_fp8_quant_cols(int x_dtype, const nstl_fp8_job* jobs, int n, void* stre
  * (by the projection epilogue), softmax scale 1/sqrt(dh), attention-probability
  * dropout.  Replaces F.scaled_dot_product_attention at utils/model.py:126-127.
  * Element (b,t,h,d) of X lives at X[(b*T + t)*X_ld + h*dh + d].
- * Three kernel families, chosen per call (same scale, LSE, dropout stream and
- * RoPE^T conventions, so they are interchangeable):
- *   one-shot MFMA : dh == 64, T % 32 == 0, T <= 256 (bf16) / 128 (f32); a head's
- *                   whole K / V in LDS, a query's score row in registers;
- *   streaming MFMA: dh == 64, bf16, T % 32 == 0, 256 < T <= 4096; key / query
- *                   tiles through LDS, online softmax (NSTL_ATTN_LONG=0: off).
- *                   With NSTL_ATTN_RAGGED_OK in flags also every ragged length
- *                   (T % 32 != 0, 1 <= T <= 4096; NSTL_ATTN_RAGGED=0: off).
- *                   With NSTL_ATTN_DH128_OK in flags also dh == 128, bf16, at every
- *                   1 <= T <= 4096 (there are no one-shot kernels at that width;
- *                   ragged T needs both flags; NSTL_ATTN_LONG=0: off).
- *                   With NSTL_ATTN_DHANY_OK in flags also every other dh % 8 == 0,
- *                   8 <= dh < 128, bf16, on the same terms as dh == 128 (dh == 64
- *                   and dh == 128 do not read this bit);
- *   generic       : everything else with dh % 8 == 0, dh <= 512, T <= 4096 (f32
- *                   past T = 128, head sizes above 128, dh != 64 or ragged T
- *                   without their flags):
- *                   one wave per row, no MFMA; a correctness path, not a
- *                   training path. */
+ * Three kernel families, interchangeable (same scale, LSE, dropout stream and RoPE^T
+ * conventions): one-shot MFMA (a head's whole K / V in LDS, a query's score row in
+ * registers), streaming MFMA (key / query tiles through LDS, online softmax) and
+ * generic (one wave per row, no MFMA; a correctness path, not a training path).
+ * Arguments outside dtype f32 / bf16, dh % 8 == 0, 8 <= dh <= 512, 1 <= T <= 4096,
+ * B, H >= 1, 0 <= p_drop < 1 are rejected.  The family of every other call, first
+ * matching row (csrc/attention_route.h: nstl::attn_route; "whole": T % 32 == 0):
+ *
+ *   dtype  dh              T                  flag(s)              switch off by        family
+ *   bf16   64              whole, > 256       -                    NSTL_ATTN_LONG=0     streaming
+ *   bf16   64              ragged             RAGGED_OK            NSTL_ATTN_LONG=0,    streaming
+ *                                                                  NSTL_ATTN_RAGGED=0
+ *   bf16   128             whole              DH128_OK             NSTL_ATTN_LONG=0     streaming
+ *   bf16   128             ragged             DH128_OK, RAGGED_OK  both, as above       streaming
+ *   bf16   8..120, not 64  whole              DHANY_OK             NSTL_ATTN_LONG=0     streaming
+ *   bf16   8..120, not 64  ragged             DHANY_OK, RAGGED_OK  both, as above       streaming
+ *   bf16   64              whole, <= 256      -                    -                    one-shot
+ *   f32    64              whole, <= 128      -                    -                    one-shot
+ *   any    any             any                -                    -                    generic
+ *
+ * A row whose flag is missing or whose switch is off does not match.  Inside one-shot,
+ * bf16: T == 128 runs the persistent forward (NSTL_ATTN_FWD=oneshot: the one-shot one),
+ * T <= 128 the fused backward (NSTL_ATTN_BWD=split: the dQ + dK/dV pair).
+ * NSTL_ROPE_BWD=table: the bf16 backward kernels read the RoPE tables instead of
+ * recomputing the angles.  The switches are environment variables read per call. */
 #define NSTL_ATTN_RAGGED_OK 1u /* flags bit 0: mask_bits / dbias_part are sized by nstl_attn_mask_words /
-                                  nstl_attn_bias_rows of these arguments, so a ragged T may take the streaming
-                                  MFMA kernels, whose keep-bit words number B*H*ceil(T/16)^2*4, not B*H*T*T/64 */
-#define NSTL_ATTN_DH128_OK 2u /* flags bit 1: a bf16 call with dh == 128 may take the streaming MFMA kernels; the
-                                 caller sizes mask_bits / dbias_part by nstl_attn_mask_words / nstl_attn_bias_rows
-                                 (both 0 without the bit: the generic kernels, which ignore them) */
-#define NSTL_ATTN_DHANY_OK 4u /* flags bit 2: the same for a bf16 call with dh % 8 == 0, 8 <= dh < 128, dh != 64
-                                 (dh == 64 and dh == 128 do not read it; 128 keeps its own bit) */
+                                  nstl_attn_bias_rows of these arguments (keep-bit words then number
+                                  B*H*ceil(T/16)^2*4, not B*H*T*T/64); see the table */
+#define NSTL_ATTN_DH128_OK 2u /* flags bit 1: the same promise for a bf16 call with dh == 128; see the table */
+#define NSTL_ATTN_DHANY_OK 4u /* flags bit 2: the same for dh % 8 == 0, 8 <= dh < 128, dh != 64; see the table */
 typedef struct nstl_attn_args {
   int dtype;
   int B, T, H, dh;
@@ -177,12 +180,11 @@ typedef struct nstl_attn_args {
   const float* rope_cos; const float* rope_sin;  /* [T][dh/2]; non-null: dq,dk rotated back */
   int rope_q, rope_k;
   float* dsum;                /* backward scratch [B*H*T] f32: rowsum(dO * O) */
-  uint64_t* mask_bits;        /* optional [B*H*T*T/64] ([nstl_attn_mask_words()] with
-                                 NSTL_ATTN_RAGGED_OK): the dropout keep bits.  Forward
+  uint64_t* mask_bits;        /* optional [nstl_attn_mask_words()] (without flags:
+                                 = B*H*T*T/64): the dropout keep bits.  Forward
                                  writes them, backward reads them instead of re-hashing
-                                 (MFMA paths: head_dim 64, 128 with
-                                 NSTL_ATTN_DH128_OK, the other widths up to 128 with
-                                 NSTL_ATTN_DHANY_OK; ignored elsewhere).  NULL:
+                                 (one-shot and streaming families of the table above;
+                                 ignored by the generic one).  NULL:
                                  both directions hash (seed, element). */
   float* dbias_part;          /* optional backward output [nstl_attn_bias_rows()][3*H*dh] f32:
                                  per-(batch, 128-row block) column sums of dq | dk | dv as
@@ -193,12 +195,30 @@ typedef struct nstl_attn_args {
 int nstl_attn_fwd(const nstl_attn_args* args, void* stream);
 int nstl_attn_bwd(const nstl_attn_args* args, void* stream);
 /* Rows of dbias_part for these arguments, or 0 when the call takes the generic
-   kernels (which do not produce it). */
+   kernels (which do not produce it) or is one nstl_attn_fwd / _bwd reject for its
+   shape (null args, dtype, dh, T, B, H, p_drop; pointers are not looked at). */
 int nstl_attn_bias_rows(const nstl_attn_args* args);
 /* Keep-bit words (uint64) of mask_bits this call would write or read: 16 x 16 tiles
    of a head, 4 words each, B*H*ceil(T/16)^2*4 on the MFMA paths (= B*H*T*T/64 when
-   T % 32 == 0), 0 on the generic path (which ignores mask_bits).  Host arithmetic. */
+   T % 32 == 0), 0 on the generic path (which ignores mask_bits) and for arguments the
+   entry points reject for their shape, as above.  Host arithmetic. */
 int64_t nstl_attn_mask_words(const nstl_attn_args* args);
+/* The route of these arguments as text, for tests and messages: host arithmetic, the
+   snprintf convention (at most n bytes written, terminated; returns the full length).
+   One of (backward != 0: the "bwd" forms):
+     rejected: <the error text of nstl_attn_fwd / nstl_attn_bwd>
+     generic <bf16|f32>
+     one-shot fwd <bf16|f32> NKT=<T/16>
+     one-shot fwd persistent[ mask]            mask: the form that stores keep bits
+     one-shot bwd fused TC=<0|128> dm=<0|1|2> rope_fast=<0|1>
+     one-shot bwd split <bf16|f32> dm=<0|1|2> rope_fast=<0|1>
+     streaming fwd DHT=<64|128>[ any <lo|hi>][ rag] drop=<0|1>
+     streaming bwd DHT=<64|128>[ any <lo|hi>][ rag] dm=<0|1|2> rope_fast=<0|1>
+   Every token but rope_fast is a template argument of the kernel(s) launched: DHT the
+   image class, any a width other than 64 / 128 with the upper 32 columns of its last
+   image absent (lo) or present (hi), rag the ragged-T form, dm the dropout mode (0 off,
+   1 stored keep bits, 2 hashed), drop = dm != 0, TC the fused backward's compile-time T. */
+int nstl_attn_route_describe(const nstl_attn_args* args, int backward, char* buf, int n);
 
 /* Post-LN residual block tail: s = x + dropout(dropout(y)); out = LN(s).
  * Replaces `src = src + self.dropoutN(src2); src = self.normN(src)` at
@@ -387,7 +407,9 @@ const char* nstl_last_error_string(void);
    2: nstl_attn_args.flags, nstl_attn_mask_words.
    3: NSTL_ATTN_DH128_OK (streaming MFMA attention at head_dim 128).
    4: NSTL_ATTN_DHANY_OK (streaming MFMA attention at every head_dim % 8 == 0 up to
-      128); no struct changed. */
+      128); no struct changed.
+   5: nstl_attn_route_describe; the attention size queries answer 0 for arguments the
+      entry points reject for their shape. */
 int nstl_version(void);
 
 /* Launch counters by kernel family, process-wide (host side, counted at each
@@ -412,9 +434,7 @@ enum {
   NSTL_K_GEMM4_SK,           /*   ... launches with a stream-K tail (grid not dividing the tiles) */
   NSTL_K_GEMM_FP8_ROPE,      /* fp8 GEMM launches with the RoPE epilogue (C5 q|k|v, cross q, cross k|v) */
   NSTL_K_GEMM4F8,            /* fp8 GEMM launches on the 4-wave persistent kernel (the rest: NSTL_K_GEMM_FP8) */
-  NSTL_K_ATTN_FWD_LONG,      /* streaming MFMA attention forward (bf16; head_dim 64: 256 < T <= 4096 and
-                                ragged T; head_dim 128 with NSTL_ATTN_DH128_OK, other widths up to 128
-                                with NSTL_ATTN_DHANY_OK: every T) */
+  NSTL_K_ATTN_FWD_LONG,      /* streaming MFMA attention forward (the table above nstl_attn_args) */
   NSTL_K_ATTN_BWD_LONG,      /*   ... its backward (dQ + dK/dV kernel pair) */
   NSTL_K_COUNT
 };

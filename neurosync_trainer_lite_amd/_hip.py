@@ -117,7 +117,8 @@ REDUCE_BATCH_MAX = 16
 EXPORTS = [
     "nstl_gemm", "nstl_gemm_grouped", "nstl_gemm_colsum_rows", "nstl_gemm_relu_mask_words",
     "nstl_gemm_workspace_bytes",
-    "nstl_attn_fwd", "nstl_attn_bwd", "nstl_attn_bias_rows", "nstl_attn_mask_words", "nstl_ln_fwd", "nstl_ln_bwd",
+    "nstl_attn_fwd", "nstl_attn_bwd", "nstl_attn_bias_rows", "nstl_attn_mask_words", "nstl_attn_route_describe",
+    "nstl_ln_fwd", "nstl_ln_bwd",
     "nstl_reduce_rows", "nstl_reduce_rows_strided", "nstl_reduce_rows3", "nstl_reduce_rows_batch",
     "nstl_colsum", "nstl_rope",
     "nstl_loss_fwd_bwd", "nstl_sumsq", "nstl_adam_step", "nstl_clip_coef", "nstl_cast", "nstl_copy2d", "nstl_autocorr",
@@ -165,6 +166,9 @@ def lib():
         if hasattr(L, "nstl_attn_mask_words"):  # absent from a version-1 build loaded for an A/B (NSTL_LIB_PATH)
             L.nstl_attn_mask_words.argtypes = [P(AttnArgs)]
             L.nstl_attn_mask_words.restype = _i64
+        if hasattr(L, "nstl_attn_route_describe"):  # version 5
+            L.nstl_attn_route_describe.argtypes = [P(AttnArgs), _i32, ctypes.c_char_p, _i32]
+            L.nstl_attn_route_describe.restype = _i32
         L.nstl_ln_fwd.argtypes = [P(LnArgs), _vp]
         L.nstl_ln_bwd.argtypes = [P(LnArgs), _vp]
         L.nstl_reduce_rows.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp]
@@ -452,12 +456,8 @@ def transpose_bf16(jobs, stream=None):
 
 
 def attn_args(dtype, B, T, H, q, q_ld, k, k_ld, v, v_ld, o, o_ld, lse, p_drop, seed, dh=64, flags=0):
-    """`flags`: ATTN_RAGGED_OK lets a ragged T (T % 32 != 0) take the streaming MFMA
-    kernels, ATTN_DH128_OK lets a bf16 call with dh = 128 take them (at every T; a
-    ragged T needs both), ATTN_DHANY_OK the same for every other dh % 8 == 0 below 128
-    (dh = 64 and 128 do not read it); mask_bits / dbias_part are then sized by
-    attn_mask_words / attn_bias_rows.  Without them dh != 64 and ragged T run the
-    generic kernels."""
+    """`flags` (ATTN_*): which kernels the call may take is the table above
+    nstl_attn_args in include/nstl.h; attn_route(a) names the ones it does take."""
     a = AttnArgs()
     a.flags = flags
     a.dtype = dtype
@@ -507,6 +507,17 @@ def attn_mask_words(a):
     version-1 build, which has no ragged path and no size query: T*T/64 per head)."""
     fn = getattr(lib(), "nstl_attn_mask_words", None)
     return fn(ctypes.byref(a)) if fn is not None else 0
+
+
+def attn_route(a, backward=False):
+    """The kernels nstl_attn_fwd (backward: nstl_attn_bwd) would run for `a`, as the text
+    of nstl_attn_route_describe (include/nstl.h); host arithmetic, nothing is launched."""
+    fn = getattr(lib(), "nstl_attn_route_describe", None)
+    if fn is None:
+        raise RuntimeError("nstl_attn_route_describe: the loaded library is older than version 5")
+    buf = ctypes.create_string_buffer(160)
+    fn(ctypes.byref(a), int(backward), buf, len(buf))
+    return buf.value.decode()
 
 
 def attn_fwd(a, stream=None):

@@ -3,8 +3,8 @@
 // autograd backward; RoPE (apply_rope_qk, :60-83) is applied to q/k by the
 // projection epilogue, and rotated back here on dq/dk).
 //
-// Shapes are short: T <= 256 frames, dh = 64 (longer bf16 windows take the streaming
-// kernels of attention_long.hip).  A whole (batch, head) key/value
+// Shapes are short: T <= 256 frames, dh = 64 (what else a call may run: the table
+// above nstl_attn_args in nstl.h).  A whole (batch, head) key/value
 // sequence fits in LDS, so there is no online softmax and no cross-workgroup
 // reduction:
 //   forward : workgroup = (b, h, 128 queries); each wave 16 queries; scores for
@@ -20,11 +20,13 @@
 // The parameter block and the helpers shared with attention_long.hip (operand
 // image, keep bits, fragment order, tile store, RoPE^T, bias partials) are in
 // attention_dev.h.
+#include <stdlib.h>
+
 #include <algorithm>
 
 #include "../../include/nstl.h"
 #include "attention_dev.h"
-#include "attention_long.h"
+#include "attention_route.h"
 #include "common.h"
 #include "status.h"
 
@@ -348,7 +350,7 @@ __global__ __launch_bounds__(FWD_NT, NKT <= 8 ? 6 : (NKT <= 12 ? 4 : 3)) void at
 // of its own.  LDS: 2 x 32 KB + 16 KB = 80 KB, two workgroups per CU.
 // Per wave and head: 4 K / V + 2 Q DMA, 4 O + 1 LSE (+ 1 keep-bit word with
 // MK) stores.
-constexpr int PF_T = 128, PF_IMG = PF_T * DH * 2, PF_KV = 4;
+constexpr int PF_T = nstl::attn::PF_T, PF_IMG = PF_T * DH * 2, PF_KV = 4;
 constexpr size_t PF_LDS = 2 * 2 * (size_t)PF_IMG + 8 * 2048;
 // raw barrier: __syncthreads() would also wait for every outstanding memory
 // operation (vmcnt(0)), i.e. for the next head's prefetch
@@ -719,7 +721,7 @@ __global__ __launch_bounds__(BWD_NT) void attn_bwd_dkv_kernel(AttnParams p) {
 //   phase 1 : S, dP over the 8 query tiles; dV += P_drop^T dO, dK += dS^T Q
 //   phase 2 : barrier; dS^T -> image; barrier; dQ = dS K
 //   stores  : barrier; dQ, dK, dV rows (+ bias column sums, last wave out)
-constexpr int FUSED_MAX_T = 128;
+constexpr int FUSED_MAX_T = nstl::attn::FUSED_MAX_T;
 // Output staging of one wave (store_tile16x64_buf): its 16 rows in four groups of
 // 4 rows (lane group g's rows 4g + r), each group padded by 32 bytes.  With
 // 128-byte rows and no padding the four lane groups' 2-byte writes land on the
@@ -1053,7 +1055,6 @@ size_t bwd_lds_bytes(int T, int esz) {  // either backward kernel (+ 2 x [8][64]
 // of 256) with the same dropout stream (drop_idx / nstl_keep), scale, LSE and
 // RoPE^T conventions, so the two paths are interchangeable.
 // ---------------------------------------------------------------------------
-constexpr int G_MAX_DH = 512, G_MAX_T = 4096;
 
 NSTL_DEV void load8(const bf16* g, float* v) {
   const bf16x8 x = *(const bf16x8*)g;
@@ -1260,32 +1261,16 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_generic(AttnParams p) {
   }
 }
 
-bool use_fast(const nstl_attn_args* a) {
-  return a->dh == DH && a->T % 32 == 0 && a->T <= (a->dtype == NSTL_BF16 ? 256 : 128);
-}
-
-// the fused backward (bf16, T <= 128); NSTL_ATTN_BWD=split selects the two
-// kernels (A/B comparisons; read per call so a test can switch it)
-bool use_fused_bwd(const nstl_attn_args* a) {
-  const char* e = getenv("NSTL_ATTN_BWD");
-  if (e && e[0] == 's') return false;
-  return use_fast(a) && a->dtype == NSTL_BF16 && a->T <= FUSED_MAX_T;
-}
-
-int fill(AttnParams& p, const nstl_attn_args* a, bool bwd) {
-  NSTL_CHECK_ARG(a != nullptr, "nstl_attn: null args");
-  NSTL_CHECK_ARG(a->dtype == NSTL_F32 || a->dtype == NSTL_BF16, "nstl_attn: bad dtype");
-  NSTL_CHECK_ARG(a->dh > 0 && a->dh % 8 == 0 && a->dh <= G_MAX_DH,
-                 "nstl_attn: head_dim must be a multiple of 8 up to %d (got %d)", G_MAX_DH, a->dh);
-  NSTL_CHECK_ARG(a->T > 0 && a->T <= G_MAX_T, "nstl_attn: T must be in [1, %d] (got %d)", G_MAX_T, a->T);
-  NSTL_CHECK_ARG(a->B > 0 && a->H > 0, "nstl_attn: empty batch");
+// the pointer, alignment and stride half of the validation (the shape half is the
+// route's), and the parameter block
+int fill(AttnParams& p, const nstl_attn_args* a, const nstl::AttnRoute& r, bool bwd) {
+  if (r.family == nstl::AttnRoute::REJECTED) return nstl::fail((int)hipErrorInvalidValue, "%s", r.why);
   NSTL_CHECK_ARG(a->q && a->k && a->v && a->o && a->lse, "nstl_attn: null tensor");
-  const int vec = a->dtype == NSTL_F32 ? 4 : 8;
+  const int vec = r.bf16 ? 8 : 4;
   NSTL_CHECK_ARG(a->q_ld % vec == 0 && a->k_ld % vec == 0 && a->v_ld % vec == 0 && a->o_ld % vec == 0,
                  "nstl_attn: ld alignment");
   NSTL_CHECK_ARG(((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) % 16 == 0,
                  "nstl_attn: tensors must be 16-byte aligned");
-  NSTL_CHECK_ARG(a->p_drop >= 0.f && a->p_drop < 1.f, "nstl_attn: p_drop out of range");
   if (bwd) {
     NSTL_CHECK_ARG(a->dout && a->dq && a->dk && a->dv, "nstl_attn_bwd: null gradient tensor");
     NSTL_CHECK_ARG(a->dout_ld % vec == 0 && (uintptr_t)a->dout % 16 == 0, "nstl_attn_bwd: dout alignment");
@@ -1293,7 +1278,7 @@ int fill(AttnParams& p, const nstl_attn_args* a, bool bwd) {
                        ((uintptr_t)a->dq | (uintptr_t)a->dk | (uintptr_t)a->dv) % 16 == 0,
                    "nstl_attn_bwd: dq/dk/dv must be 16-byte aligned");
     NSTL_CHECK_ARG(!(a->rope_q || a->rope_k) || (a->rope_cos && a->rope_sin), "nstl_attn_bwd: rope tables");
-    const bool mfma = use_fast(a) || nstl::attn_long_takes(a);
+    const bool mfma = nstl::attn_mfma(r);
     NSTL_CHECK_ARG(!mfma || a->dsum, "nstl_attn_bwd: dsum scratch [B*H*T] f32 missing");
     NSTL_CHECK_ARG(!a->dbias_part || mfma, "nstl_attn_bwd: dbias_part needs an MFMA path (head_dim 64, or another width up to 128 with its flag)");
   }
@@ -1311,10 +1296,7 @@ int fill(AttnParams& p, const nstl_attn_args* a, bool bwd) {
   p.dv = (char*)a->dv; p.dv_ld = a->dv_ld;
   p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin;
   p.rope_q = a->rope_q; p.rope_k = a->rope_k;
-  {  // NSTL_ROPE_BWD=table: the bf16 backward kernels read the tables (A/B; read per call)
-    const char* e = getenv("NSTL_ROPE_BWD");
-    p.rope_fast = !(e && e[0] == 't');
-  }
+  p.rope_fast = r.rope_fast;
   p.B = a->B; p.T = a->T; p.H = a->H; p.dh = a->dh;
   p.scale = 1.0f / sqrtf((float)a->dh);
   p.thresh = nstl_drop_thresh(a->p_drop);
@@ -1325,122 +1307,178 @@ int fill(AttnParams& p, const nstl_attn_args* a, bool bwd) {
   return 0;
 }
 
-// the persistent forward (bf16, T = 128, enough heads to fill the grid);
-// NSTL_ATTN_FWD=oneshot selects the one-workgroup-per-head kernel (A/B; read per call)
-bool use_persist_fwd(const nstl_attn_args* a) {
-  const char* e = getenv("NSTL_ATTN_FWD");
-  if (e && e[0] == 'o') return false;
-  return a->dtype == NSTL_BF16 && a->T == PF_T && a->dh == DH;
+// Grid and dynamic LDS of each family's launches.  Generic: one wave per row, four
+// rows per workgroup, the wave's own row(s) and its score row(s) in LDS as f32.
+dim3 generic_grid(const AttnParams& p) { return dim3((p.T + 3) / 4, p.B * p.H); }
+size_t generic_lds_bytes(const AttnParams& p, int own_rows, int score_rows) {
+  return 4 * (size_t)(own_rows * p.dh + score_rows * p.T) * 4;
 }
+// one-shot forward / split backward: 128 rows of a (batch, head) per workgroup
+static_assert(FWD_QB == BWD_ROWS, "one grid for the one-shot forward and the split backward");
+dim3 oneshot_grid(const AttnParams& p) { return dim3((p.T + BWD_ROWS - 1) / BWD_ROWS, p.B * p.H); }
 
 // the split backward: dQ (also writes D = rowsum(dO * O)), then dK / dV
-template <typename T, int DM>
-int launch_split(dim3 grid, size_t lds, hipStream_t st, const AttnParams& p) {
+template <typename T>
+int split_bwd(const nstl::AttnRoute& r, const AttnParams& p, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_BWD_SPLIT);
-  int rc = launch(attn_bwd_dq_kernel<T, DM>, grid, lds, st, p, "nstl_attn_bwd dq", BWD_NT);
-  if (rc) return rc;
-  return launch(attn_bwd_dkv_kernel<T, DM>, grid, lds, st, p, "nstl_attn_bwd dkv", BWD_NT);
+  const size_t lds = bwd_lds_bytes(p.T, (int)sizeof(T));
+  int rc = 0;
+  nstl::with_const<0, 1, 2>(r.dm, [&](auto DM) {
+    rc = launch(attn_bwd_dq_kernel<T, DM()>, oneshot_grid(p), lds, st, p, "nstl_attn_bwd dq", BWD_NT);
+    if (!rc) rc = launch(attn_bwd_dkv_kernel<T, DM()>, oneshot_grid(p), lds, st, p, "nstl_attn_bwd dkv", BWD_NT);
+  });
+  return rc;
 }
 
 }  // namespace
 
+namespace nstl {
+AttnRoute attn_route(const nstl_attn_args* a) {
+  using namespace attn;
+  static_assert(DH == ONESHOT_DH, "the one-shot kernels' head width");
+  AttnRoute r = {};
+  r.family = AttnRoute::REJECTED;
+#define NSTL_ROUTE_CHECK(cond, ...) \
+  if (!(cond)) return snprintf(r.why, sizeof(r.why), __VA_ARGS__), r
+  NSTL_ROUTE_CHECK(a != nullptr, "nstl_attn: null args");
+  NSTL_ROUTE_CHECK(a->dtype == NSTL_F32 || a->dtype == NSTL_BF16, "nstl_attn: bad dtype");
+  NSTL_ROUTE_CHECK(a->dh > 0 && a->dh % 8 == 0 && a->dh <= G_MAX_DH,
+                   "nstl_attn: head_dim must be a multiple of 8 up to %d (got %d)", G_MAX_DH, a->dh);
+  NSTL_ROUTE_CHECK(a->T > 0 && a->T <= G_MAX_T, "nstl_attn: T must be in [1, %d] (got %d)", G_MAX_T, a->T);
+  NSTL_ROUTE_CHECK(a->B > 0 && a->H > 0, "nstl_attn: empty batch");
+  NSTL_ROUTE_CHECK(a->p_drop >= 0.f && a->p_drop < 1.f, "nstl_attn: p_drop out of range");
+#undef NSTL_ROUTE_CHECK
+  // the switches (A/B arms; read per call so that a test can flip them)
+  auto is = [](const char* e, char c) { return e && e[0] == c; };
+  const bool no_long = is(getenv("NSTL_ATTN_LONG"), '0');        // streaming off
+  const bool no_ragged = is(getenv("NSTL_ATTN_RAGGED"), '0');    // streaming off at T % 32 != 0
+  const bool fwd_oneshot = is(getenv("NSTL_ATTN_FWD"), 'o');     // "oneshot": no persistent forward
+  const bool bwd_split = is(getenv("NSTL_ATTN_BWD"), 's');       // "split": no fused backward
+  r.rope_fast = !is(getenv("NSTL_ROPE_BWD"), 't');               // "table": the bf16 backward reads the tables
+  r.bf16 = a->dtype == NSTL_BF16;
+  r.dm = !nstl_drop_thresh(a->p_drop) ? 0 : (a->mask_bits ? 1 : 2);
+  r.drop = r.dm != 0;
+  const int dh = a->dh, T = a->T;
+  const bool whole = T % 32 == 0;
+  const bool width_ok = dh == ONESHOT_DH || (dh == LONG_MAX_DH ? (a->flags & NSTL_ATTN_DH128_OK) != 0
+                                                               : dh < LONG_MAX_DH && (a->flags & NSTL_ATTN_DHANY_OK));
+  // head_dim 64 has one-shot kernels up to their limit; a ragged T has no others at any width
+  const bool length_ok = whole ? dh != ONESHOT_DH || T > ONESHOT_MAX_T_BF16 : (a->flags & NSTL_ATTN_RAGGED_OK) && !no_ragged;
+  if (!no_long && r.bf16 && T <= LONG_MAX_T && width_ok && length_ok) {
+    r.family = AttnRoute::STREAMING;
+    r.dht = dh <= 64 ? 64 : 128;
+    r.any = dh != 64 && dh != 128;
+    r.hi = !r.any || dh > r.dht - 32;
+    r.rag = r.any || !whole;
+  } else if (dh == ONESHOT_DH && whole && T <= (r.bf16 ? ONESHOT_MAX_T_BF16 : ONESHOT_MAX_T_F32)) {
+    r.family = AttnRoute::ONESHOT;
+    r.nkt = T / 16;
+    r.persist = !fwd_oneshot && r.bf16 && T == PF_T;
+    r.fused = !bwd_split && r.bf16 && T <= FUSED_MAX_T;
+    r.tc = T == FUSED_MAX_T ? FUSED_MAX_T : 0;
+  } else {
+    r.family = AttnRoute::GENERIC;
+  }
+  return r;
+}
+}  // namespace nstl
+
 extern "C" int nstl_attn_fwd(const nstl_attn_args* a, void* stream) {
+  const nstl::AttnRoute r = nstl::attn_route(a);
   AttnParams p;
-  int rc = fill(p, a, false);
+  int rc = fill(p, a, r, false);
   if (rc) return rc;
-  const int esz = a->dtype == NSTL_F32 ? 4 : 2;
   hipStream_t st = (hipStream_t)stream;
-  if (nstl::attn_long_takes(a)) return nstl::attn_long_fwd(p, st);  // bf16, 256 < T: streaming kernels
-  if (!use_fast(a)) {
+  if (r.family == nstl::AttnRoute::STREAMING) return nstl::attn_long_fwd(p, r, st);
+  if (r.family == nstl::AttnRoute::GENERIC) {
     nstl::count(NSTL_K_ATTN_FWD_GENERIC);
-    dim3 grid((a->T + 3) / 4, a->B * a->H);
-    const size_t lds = 4 * (size_t)(a->dh + a->T) * 4;
-    if (a->dtype == NSTL_BF16) return launch(attn_fwd_generic<bf16>, grid, lds, st, p, "nstl_attn_fwd generic", NT);
-    return launch(attn_fwd_generic<float>, grid, lds, st, p, "nstl_attn_fwd generic", NT);
+    const size_t lds = generic_lds_bytes(p, 1, 1);
+    return r.bf16 ? launch(attn_fwd_generic<bf16>, generic_grid(p), lds, st, p, "nstl_attn_fwd generic", NT)
+                  : launch(attn_fwd_generic<float>, generic_grid(p), lds, st, p, "nstl_attn_fwd generic", NT);
   }
   nstl::count(NSTL_K_ATTN_FWD);
-  if (use_persist_fwd(a)) {
+  if (r.persist) {
     // head buffers (q, k, v, o): T rows of each as one 32-bit extent
-    NSTL_CHECK_ARG((int64_t)a->T * std::max(std::max(a->q_ld, a->k_ld), std::max(a->v_ld, a->o_ld)) * 2 < (1ll << 31),
+    NSTL_CHECK_ARG((int64_t)p.T * std::max(std::max(p.q_ld, p.k_ld), std::max(p.v_ld, p.o_ld)) * 2 < (1ll << 31),
                    "nstl_attn_fwd: T x row stride past 2^31 bytes");
-    const int nitems = a->B * a->H;
-    const int G = std::min(nitems, std::max(2, 2 * nstl::stream_cus(st)));  // two workgroups per CU the stream may use
-    const size_t lds = PF_LDS;
-    if (p.thresh && p.mask)
-      return launch(attn_fwd_persist_kernel<true>, dim3(G), lds, st, p, "nstl_attn_fwd persistent", FWD_NT, nitems);
-    return launch(attn_fwd_persist_kernel<false>, dim3(G), lds, st, p, "nstl_attn_fwd persistent", FWD_NT, nitems);
+    const int nitems = p.B * p.H;
+    const dim3 grid(std::min(nitems, std::max(2, 2 * nstl::stream_cus(st))));  // two workgroups per CU the stream may use
+    return r.dm == 1 ? launch(attn_fwd_persist_kernel<true>, grid, PF_LDS, st, p, "nstl_attn_fwd persistent", FWD_NT, nitems)
+                     : launch(attn_fwd_persist_kernel<false>, grid, PF_LDS, st, p, "nstl_attn_fwd persistent", FWD_NT, nitems);
   }
-  dim3 grid((a->T + FWD_QB - 1) / FWD_QB, a->B * a->H);
-  const size_t lds = fwd_lds_bytes(a->T, esz);
-  // T % 32 == 0 and T <= 256 on this path: NKT in {2, 4, ..., 16}
-#define NSTL_FWD_CASE(N)                                                                              \
-  case N:                                                                                             \
-    return a->dtype == NSTL_BF16 ? launch(attn_fwd_kernel<bf16, N>, grid, lds, st, p, "nstl_attn_fwd", FWD_NT) \
-                                 : launch(attn_fwd_kernel<float, N>, grid, lds, st, p, "nstl_attn_fwd", FWD_NT);
-  switch (a->T / 16) {
-    NSTL_FWD_CASE(2) NSTL_FWD_CASE(4) NSTL_FWD_CASE(6) NSTL_FWD_CASE(8)
-    NSTL_FWD_CASE(10) NSTL_FWD_CASE(12) NSTL_FWD_CASE(14) NSTL_FWD_CASE(16)
-  }
-#undef NSTL_FWD_CASE
-  return nstl::fail((int)hipErrorInvalidValue, "nstl_attn_fwd: T=%d off the MFMA path", a->T);
+  const size_t lds = fwd_lds_bytes(p.T, r.bf16 ? 2 : 4);
+  const bool found = nstl::with_const<2, 4, 6, 8, 10, 12, 14, 16>(r.nkt, [&](auto NKT) {
+    rc = r.bf16 ? launch(attn_fwd_kernel<bf16, NKT()>, oneshot_grid(p), lds, st, p, "nstl_attn_fwd", FWD_NT)
+                : launch(attn_fwd_kernel<float, NKT()>, oneshot_grid(p), lds, st, p, "nstl_attn_fwd", FWD_NT);
+  });
+  return found ? rc : nstl::fail((int)hipErrorInvalidValue, "nstl_attn_fwd: T=%d off the MFMA path", p.T);
 }
 
 extern "C" int nstl_attn_bwd(const nstl_attn_args* a, void* stream) {
+  const nstl::AttnRoute r = nstl::attn_route(a);
   AttnParams p;
-  int rc = fill(p, a, true);
+  int rc = fill(p, a, r, true);
   if (rc) return rc;
-  const int esz = a->dtype == NSTL_F32 ? 4 : 2;
   hipStream_t st = (hipStream_t)stream;
-  if (nstl::attn_long_takes(a)) return nstl::attn_long_bwd(p, st);
-  if (!use_fast(a)) {
+  if (r.family == nstl::AttnRoute::STREAMING) return nstl::attn_long_bwd(p, r, st);
+  if (r.family == nstl::AttnRoute::GENERIC) {
     nstl::count(NSTL_K_ATTN_BWD_GENERIC);
-    dim3 grid((a->T + 3) / 4, a->B * a->H);
-    const size_t lq = 4 * (size_t)(2 * a->dh + a->T) * 4, lkv = 4 * (size_t)(2 * a->dh + 2 * a->T) * 4;
-    if (a->dtype == NSTL_BF16) {
-      if ((rc = launch(attn_bwd_dq_generic<bf16>, grid, lq, st, p, "nstl_attn_bwd generic dq", NT))) return rc;
-      return launch(attn_bwd_dkv_generic<bf16>, grid, lkv, st, p, "nstl_attn_bwd generic dkv", NT);
-    }
-    if ((rc = launch(attn_bwd_dq_generic<float>, grid, lq, st, p, "nstl_attn_bwd generic dq", NT))) return rc;
-    return launch(attn_bwd_dkv_generic<float>, grid, lkv, st, p, "nstl_attn_bwd generic dkv", NT);
+    auto pair = [&](auto dq, auto dkv) {
+      int e = launch(dq, generic_grid(p), generic_lds_bytes(p, 2, 1), st, p, "nstl_attn_bwd generic dq", NT);
+      return e ? e : launch(dkv, generic_grid(p), generic_lds_bytes(p, 2, 2), st, p, "nstl_attn_bwd generic dkv", NT);
+    };
+    return r.bf16 ? pair(attn_bwd_dq_generic<bf16>, attn_bwd_dkv_generic<bf16>)
+                  : pair(attn_bwd_dq_generic<float>, attn_bwd_dkv_generic<float>);
   }
-  if (use_fused_bwd(a)) {
-    NSTL_CHECK_ARG(!(a->rope_q || a->rope_k) || ((((uintptr_t)a->rope_cos) | ((uintptr_t)a->rope_sin)) & 15) == 0,
+  if (r.fused) {
+    NSTL_CHECK_ARG(!(p.rope_q || p.rope_k) || ((((uintptr_t)p.rope_cos) | ((uintptr_t)p.rope_sin)) & 15) == 0,
                    "nstl_attn_bwd: RoPE tables must be 16-byte aligned");
     // head_rsrc: T rows of each operand as one buffer (32-bit extent)
-    const int64_t ld_max = std::max(std::max(std::max(a->q_ld, a->k_ld), std::max(std::max(a->v_ld, a->o_ld), a->dout_ld)),
-                                    std::max(std::max(a->dq_ld, a->dk_ld), a->dv_ld));
-    NSTL_CHECK_ARG((int64_t)a->T * ld_max * 2 < (1ll << 31), "nstl_attn_bwd: T x row stride past 2^31 bytes");
+    const int64_t ld_max = std::max(std::max(std::max(p.q_ld, p.k_ld), std::max(std::max(p.v_ld, p.o_ld), p.dout_ld)),
+                                    std::max(std::max(p.dq_ld, p.dk_ld), p.dv_ld));
+    NSTL_CHECK_ARG((int64_t)p.T * ld_max * 2 < (1ll << 31), "nstl_attn_bwd: T x row stride past 2^31 bytes");
     nstl::count(NSTL_K_ATTN_BWD_FUSED);
-    const dim3 grid(1, a->B * a->H);
-    if (a->T == FUSED_MAX_T) {  // the production shape: T a compile-time constant
-      if (!p.thresh) return launch(attn_bwd_fused_kernel<0, FUSED_MAX_T>, grid, FUSED_LDS, st, p, "nstl_attn_bwd fused", BWD_NT);
-      if (p.mask) return launch(attn_bwd_fused_kernel<1, FUSED_MAX_T>, grid, FUSED_LDS, st, p, "nstl_attn_bwd fused", BWD_NT);
-      return launch(attn_bwd_fused_kernel<2, FUSED_MAX_T>, grid, FUSED_LDS, st, p, "nstl_attn_bwd fused", BWD_NT);
-    }
-    if (!p.thresh) return launch(attn_bwd_fused_kernel<0>, grid, FUSED_LDS, st, p, "nstl_attn_bwd fused", BWD_NT);
-    if (p.mask) return launch(attn_bwd_fused_kernel<1>, grid, FUSED_LDS, st, p, "nstl_attn_bwd fused", BWD_NT);
-    return launch(attn_bwd_fused_kernel<2>, grid, FUSED_LDS, st, p, "nstl_attn_bwd fused", BWD_NT);
+    // TC: T = FUSED_MAX_T, the production shape, as a compile-time constant
+    nstl::with_const<FUSED_MAX_T, 0>(r.tc, [&](auto TC) {
+      nstl::with_const<0, 1, 2>(r.dm, [&](auto DM) {
+        rc = launch(attn_bwd_fused_kernel<DM(), TC()>, dim3(1, p.B * p.H), FUSED_LDS, st, p, "nstl_attn_bwd fused", BWD_NT);
+      });
+    });
+    return rc;
   }
-  dim3 grid((a->T + BWD_ROWS - 1) / BWD_ROWS, a->B * a->H);
-  const size_t lds = bwd_lds_bytes(a->T, esz);
-  const int dm = !p.thresh ? 0 : (p.mask ? 1 : 2);
-  if (a->dtype == NSTL_BF16) {
-    if (dm == 0) return launch_split<bf16, 0>(grid, lds, st, p);
-    if (dm == 1) return launch_split<bf16, 1>(grid, lds, st, p);
-    return launch_split<bf16, 2>(grid, lds, st, p);
-  }
-  if (dm == 0) return launch_split<float, 0>(grid, lds, st, p);
-  if (dm == 1) return launch_split<float, 1>(grid, lds, st, p);
-  return launch_split<float, 2>(grid, lds, st, p);
+  return r.bf16 ? split_bwd<bf16>(r, p, st) : split_bwd<float>(r, p, st);
 }
 
 extern "C" int nstl_attn_bias_rows(const nstl_attn_args* a) {
-  if (a == nullptr || !(use_fast(a) || nstl::attn_long_takes(a))) return 0;
-  return a->B * ((a->T + BWD_ROWS - 1) / BWD_ROWS);
+  const nstl::AttnRoute r = nstl::attn_route(a);
+  return nstl::attn_mfma(r) ? a->B * ((a->T + BWD_ROWS - 1) / BWD_ROWS) : 0;
 }
 
 extern "C" int64_t nstl_attn_mask_words(const nstl_attn_args* a) {
-  if (a == nullptr || !(use_fast(a) || nstl::attn_long_takes(a))) return 0;
+  const nstl::AttnRoute r = nstl::attn_route(a);
+  if (!nstl::attn_mfma(r)) return 0;
   const int64_t nt = (a->T + 15) / 16;
   return (int64_t)a->B * a->H * nt * nt * 4;
+}
+
+extern "C" int nstl_attn_route_describe(const nstl_attn_args* a, int backward, char* buf, int n) {
+  const nstl::AttnRoute r = nstl::attn_route(a);
+  const size_t cap = buf && n > 0 ? (size_t)n : 0;
+  const char* ty = r.bf16 ? "bf16" : "f32";
+  switch (r.family) {
+    case nstl::AttnRoute::REJECTED: return snprintf(buf, cap, "rejected: %s", r.why);
+    case nstl::AttnRoute::GENERIC: return snprintf(buf, cap, "generic %s", ty);
+    case nstl::AttnRoute::ONESHOT:
+      if (!backward)
+        return r.persist ? snprintf(buf, cap, "one-shot fwd persistent%s", r.dm == 1 ? " mask" : "")
+                         : snprintf(buf, cap, "one-shot fwd %s NKT=%d", ty, r.nkt);
+      return r.fused ? snprintf(buf, cap, "one-shot bwd fused TC=%d dm=%d rope_fast=%d", r.tc, r.dm, r.rope_fast)
+                     : snprintf(buf, cap, "one-shot bwd split %s dm=%d rope_fast=%d", ty, r.dm, r.rope_fast);
+    case nstl::AttnRoute::STREAMING: {
+      const char* form = r.any ? (r.hi ? " any hi rag" : " any lo rag") : (r.rag ? " rag" : "");
+      return backward ? snprintf(buf, cap, "streaming bwd DHT=%d%s dm=%d rope_fast=%d", r.dht, form, r.dm, r.rope_fast)
+                      : snprintf(buf, cap, "streaming fwd DHT=%d%s drop=%d", r.dht, form, (int)r.drop);
+    }
+  }
+  return -1;
 }

@@ -1,10 +1,7 @@
-// Streaming MFMA attention for long windows (bf16, head_dim 64, T % 32 == 0,
-// 256 < T <= 4096): the shapes past the one-shot kernels of attention.hip, whose
-// score rows live in registers and whose K / V of a whole head live in LDS; and,
-// for a caller that sets NSTL_ATTN_RAGGED_OK, for every ragged window (T % 32 != 0,
-// 1 <= T <= 4096), which the one-shot kernels do not take at any length; and, for a
-// caller that sets NSTL_ATTN_DH128_OK, for head_dim 128 at every window length (the
-// one-shot kernels are head_dim 64 only).
+// Streaming MFMA attention (bf16): the shapes past the one-shot kernels of
+// attention.hip, whose score rows live in registers and whose K / V of a whole head
+// live in LDS.  Which calls come here: the table above nstl_attn_args in nstl.h
+// (decided by nstl::attn_route, attention_route.h).
 //
 // The head width is the template parameter DHT of the three kernels (64 or 128).  A
 // 128-wide head is two 64-column halves: every K / V / Q / dO tile is two
@@ -14,8 +11,8 @@
 // rotated (RoPE^T pair index 32 half + ...) and column-summed one half at a time.  The
 // <64, ...> instantiations are the kernels as they were before DHT.
 //
-// Every other width dh % 8 == 0 below 128 (a caller that sets NSTL_ATTN_DHANY_OK) runs
-// the ANY instantiations: DHT is then the image class (64: dh <= 56 in one image, 128:
+// Every other width dh % 8 == 0 below 128 runs the ANY instantiations: DHT is then
+// the image class (64: dh <= 56 in one image, 128:
 // 72 <= dh <= 120 in two) and the width is p.dh.  Columns at and past dh are absent:
 // their DMA pieces are fetched from piece 0 of the same head's row (TileDmaW), the
 // wave's own-row fragments are exact zeros there (row_frag_w), nothing is stored,
@@ -60,11 +57,9 @@
 // row; the dK / dV kernel's LSE / D rows in LDS are padded to whole tiles with
 // +inf / 0; keep bits of rows and keys past T are stored as 0; the keep-bit words
 // have ceil(T / 16) tiles a side.
-#include <stdlib.h>
-
 #include "../../include/nstl.h"
 #include "attention_dev.h"
-#include "attention_long.h"
+#include "attention_route.h"
 #include "common.h"
 #include "status.h"
 
@@ -82,7 +77,6 @@ template <int DHT> struct Geo {
   // waves per SIMD the forward and dQ kernels are compiled for
   static constexpr int OCC = DHT == 64 ? 4 : 2;
 };
-constexpr int LONG_MIN_T = 256, LONG_MAX_T = 4096;        // (one-shot limit, T range of nstl_attn]
 
 // f(half 0), then f(half 1) of a 128-wide head, the half a compile-time constant (the
 // backward epilogues).  In the backward tile loops the second half is instead an
@@ -601,11 +595,12 @@ __global__ __launch_bounds__(LNT, Geo<DHT>::OCC) void attn_bwd_dq_long_kernel(At
 // rows of each of the LSE / D arrays: T, or (ragged T) T rounded up to whole
 // 64-query tiles -- the padding rows hold lse = +inf / D = 0, and both arrays stay
 // 16-byte aligned for ds_read_b128.  head_dim 128: the tile buffers are 64 KB and
-// the bias partials [dk | dv][half][NW][64]; 104 KB at T = 4096.
-int dkv_rows(int T) { return T % 32 == 0 ? T : (T + KT - 1) / KT * KT; }
+// the bias partials [dk | dv][half][NW][64]; 104 KB at T = 4096.  rag: the kernel's
+// RAG (a runtime-width call is ragged at every T, so it pads at T % 32 == 0 too).
+int dkv_rows(int T, bool rag) { return rag ? (T + KT - 1) / KT * KT : T; }
 template <int DHT> NSTL_DEV int dkv_red_off(int rows) { return 2 * Geo<DHT>::BUF_B + 2 * rows * 4; }
-template <int DHT> size_t dkv_lds_bytes(int T) {
-  return (size_t)2 * Geo<DHT>::BUF_B + (size_t)2 * dkv_rows(T) * 4 + 2 * Geo<DHT>::NH * NW * 64 * 4 + 16;
+template <int DHT> size_t dkv_lds_bytes(int T, bool rag) {
+  return (size_t)2 * Geo<DHT>::BUF_B + (size_t)2 * dkv_rows(T, rag) * 4 + 2 * Geo<DHT>::NH * NW * 64 * 4 + 16;
 }
 
 template <int DHT, int DM, bool RAG = false, bool ANY = false, bool HI = true>
@@ -616,7 +611,7 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   constexpr bool last_kc = !ANY || HI;  // the last 32-column k-chunk (accumulator tiles 2, 3 of the last half) exists
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int T_ = p.T, nt16 = (T_ + 15) / 16, ntile = (T_ + KT - 1) / KT;
-  const int Tp = RAG ? ntile * KT : T_;  // dkv_rows(T)
+  const int Tp = RAG ? ntile * KT : T_;  // dkv_rows(T, RAG)
   float* lse_s = (float*)(smem + 2 * BUF_B);
   float* dq_s = lse_s + Tp;
   float* red = (float*)(smem + dkv_red_off<DHT>(Tp));  // [2][NH][NW][64]
@@ -853,113 +848,43 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long_kernel(AttnParams p) {
   });
 }
 
-template <int DHT, int DM, bool RAG>
-int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
-  int rc = launch(attn_bwd_dq_long_kernel<DHT, DM, RAG>, grid, DqLds<DHT>::BYTES, st, p, "nstl_attn_bwd long dq", LNT);
-  if (rc) return rc;
-  return launch(attn_bwd_dkv_long_kernel<DHT, DM, RAG>, grid, dkv_lds_bytes<DHT>(p.T), st, p, "nstl_attn_bwd long dkv",
-                LNT);
+// The route's run-time fields as the template arguments <DHT, M, RAG, ANY, HI> of a
+// generic lambda, M (one of MS...) the forward's DROP or the backward's DM.  The four
+// branches are the forms that exist: a runtime width (ANY) is always ragged and is the
+// only one with a lower half (!HI).
+template <int... MS, class F>
+int with_kernel_args(const nstl::AttnRoute& r, int m, const char* what, F&& f) {
+  using Y = std::true_type;
+  using N = std::false_type;
+  int rc = 0;
+  const bool found = nstl::with_const<64, 128>(r.dht, [&](auto DHT) {
+    nstl::with_const<MS...>(m, [&](auto M) {
+      if (r.any) rc = r.hi ? f(DHT, M, Y{}, Y{}, Y{}) : f(DHT, M, Y{}, Y{}, N{});
+      else rc = r.rag ? f(DHT, M, Y{}, N{}, Y{}) : f(DHT, M, N{}, N{}, Y{});
+    });
+  });
+  return found ? rc : nstl::fail((int)hipErrorInvalidValue, "%s: no streaming kernel of image class %d", what, r.dht);
 }
-template <int DHT, int DM>
-int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
-  return p.T % 32 ? launch_bwd<DHT, DM, true>(grid, st, p) : launch_bwd<DHT, DM, false>(grid, st, p);
-}
-template <int DHT>
-int launch_bwd(dim3 grid, hipStream_t st, const AttnParams& p) {
-  if (!p.thresh) return launch_bwd<DHT, 0>(grid, st, p);
-  if (p.mask) return launch_bwd<DHT, 1>(grid, st, p);
-  return launch_bwd<DHT, 2>(grid, st, p);
-}
-// Head widths other than 64 and 128 (8 <= dh < 128, dh % 8 == 0): DHT is the image
-// class (64: one image, 128: two), HI whether the last image's upper 32 columns hold
-// anything, the width itself is p.dh.  One instantiation per class, half and dropout
-// mode serves every T: the ragged form, which at T % 32 == 0 only pads the dK / dV
-// kernel's LSE / D rows to whole tiles (dkv_rows_any).
-int dkv_rows_any(int T) { return (T + KT - 1) / KT * KT; }
-template <int DHT> size_t dkv_lds_bytes_any(int T) {
-  return (size_t)2 * Geo<DHT>::BUF_B + (size_t)2 * dkv_rows_any(T) * 4 + 2 * Geo<DHT>::NH * NW * 64 * 4 + 16;
-}
-template <int DHT, int DM, bool HI>
-int launch_bwd_any(dim3 grid, hipStream_t st, const AttnParams& p) {
-  int rc = launch(attn_bwd_dq_long_kernel<DHT, DM, true, true, HI>, grid, DqLds<DHT>::BYTES, st, p,
-                  "nstl_attn_bwd long dq", LNT);
-  if (rc) return rc;
-  return launch(attn_bwd_dkv_long_kernel<DHT, DM, true, true, HI>, grid, dkv_lds_bytes_any<DHT>(p.T), st, p,
-                "nstl_attn_bwd long dkv", LNT);
-}
-template <int DHT, bool HI>
-int launch_bwd_any(dim3 grid, hipStream_t st, const AttnParams& p) {
-  if (!p.thresh) return launch_bwd_any<DHT, 0, HI>(grid, st, p);
-  if (p.mask) return launch_bwd_any<DHT, 1, HI>(grid, st, p);
-  return launch_bwd_any<DHT, 2, HI>(grid, st, p);
-}
-template <int DHT, bool HI>
-int launch_fwd_any(dim3 grid, hipStream_t st, const AttnParams& p) {
-  constexpr size_t lds = 2 * Geo<DHT>::BUF_B;
-  if (p.thresh)
-    return launch(attn_fwd_long_kernel<DHT, true, true, true, HI>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
-  return launch(attn_fwd_long_kernel<DHT, false, true, true, HI>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
-}
-// image class and half of a runtime width: 8..32 <64, lo>, 40..56 <64, hi>, 72..96 <128, lo>, 104..120 <128, hi>
-template <typename F64L, typename F64H, typename F128L, typename F128H>
-int by_width(int dh, F64L f64l, F64H f64h, F128L f128l, F128H f128h) {
-  if (dh < 64) return dh > 32 ? f64h() : f64l();
-  return dh > 96 ? f128h() : f128l();
-}
-template <int DHT>
-int launch_fwd(dim3 grid, hipStream_t st, const AttnParams& p) {
-  constexpr size_t lds = 2 * Geo<DHT>::BUF_B;
-  if (p.T % 32) {
-    if (p.thresh) return launch(attn_fwd_long_kernel<DHT, true, true>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
-    return launch(attn_fwd_long_kernel<DHT, false, true>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
-  }
-  if (p.thresh) return launch(attn_fwd_long_kernel<DHT, true>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
-  return launch(attn_fwd_long_kernel<DHT, false>, grid, lds, st, p, "nstl_attn_fwd long", LNT);
-}
+dim3 long_grid(const AttnParams& p) { return dim3((p.T + ROWS - 1) / ROWS, p.B * p.H); }
+template <int DHT> constexpr size_t fwd_lds_bytes() { return 2 * Geo<DHT>::BUF_B; }
 
 }  // namespace
 
-namespace nstl {
-
-bool attn_long_takes(const nstl_attn_args* a) {
-  const char* e = getenv("NSTL_ATTN_LONG");
-  if (e && e[0] == '0') return false;
-  if (a->dtype != NSTL_BF16 || a->T <= 0 || a->T > LONG_MAX_T) return false;
-  if (a->dh == 128) {
-    // head_dim 128 has no one-shot kernels: whole tiles stream at every length, for a
-    // caller that asked for it (without the bit: the generic kernels, as in version 2)
-    if (!(a->flags & NSTL_ATTN_DH128_OK)) return false;
-    if (a->T % 32 == 0) return true;
-  } else if (a->dh == DH) {
-    if (a->T % 32 == 0) return a->T > LONG_MIN_T;
-  } else {
-    // every other width up to 128 (fill() has checked dh % 8 == 0): the same, behind a bit of its own
-    if (a->dh <= 0 || a->dh % 8 || a->dh > 128 || !(a->flags & NSTL_ATTN_DHANY_OK)) return false;
-    if (a->T % 32 == 0) return true;
-  }
-  // ragged T, any length: only for a caller whose side buffers are sized for it
-  e = getenv("NSTL_ATTN_RAGGED");
-  return (a->flags & NSTL_ATTN_RAGGED_OK) && !(e && e[0] == '0');
-}
-
-int attn_long_fwd(const AttnParams& p, hipStream_t st) {
+int nstl::attn_long_fwd(const AttnParams& p, const AttnRoute& r, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_FWD_LONG);
-  const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
-  if (p.dh != 64 && p.dh != 128)
-    return by_width(
-        p.dh, [&] { return launch_fwd_any<64, false>(grid, st, p); }, [&] { return launch_fwd_any<64, true>(grid, st, p); },
-        [&] { return launch_fwd_any<128, false>(grid, st, p); }, [&] { return launch_fwd_any<128, true>(grid, st, p); });
-  return p.dh == 128 ? launch_fwd<128>(grid, st, p) : launch_fwd<64>(grid, st, p);
+  return with_kernel_args<0, 1>(r, r.drop, "nstl_attn_fwd long", [&](auto DHT, auto DROP, auto RAG, auto ANY, auto HI) {
+    return launch(attn_fwd_long_kernel<DHT(), DROP() != 0, RAG(), ANY(), HI()>, long_grid(p), fwd_lds_bytes<DHT()>(), st, p,
+                  "nstl_attn_fwd long", LNT);
+  });
 }
 
-int attn_long_bwd(const AttnParams& p, hipStream_t st) {
+int nstl::attn_long_bwd(const AttnParams& p, const AttnRoute& r, hipStream_t st) {
   nstl::count(NSTL_K_ATTN_BWD_LONG);
-  const dim3 grid((p.T + ROWS - 1) / ROWS, p.B * p.H);
-  if (p.dh != 64 && p.dh != 128)
-    return by_width(
-        p.dh, [&] { return launch_bwd_any<64, false>(grid, st, p); }, [&] { return launch_bwd_any<64, true>(grid, st, p); },
-        [&] { return launch_bwd_any<128, false>(grid, st, p); }, [&] { return launch_bwd_any<128, true>(grid, st, p); });
-  return p.dh == 128 ? launch_bwd<128>(grid, st, p) : launch_bwd<64>(grid, st, p);
+  return with_kernel_args<0, 1, 2>(r, r.dm, "nstl_attn_bwd long", [&](auto DHT, auto DM, auto RAG, auto ANY, auto HI) {
+    int rc = launch(attn_bwd_dq_long_kernel<DHT(), DM(), RAG(), ANY(), HI()>, long_grid(p), DqLds<DHT()>::BYTES, st, p,
+                    "nstl_attn_bwd long dq", LNT);
+    if (rc) return rc;
+    return launch(attn_bwd_dkv_long_kernel<DHT(), DM(), RAG(), ANY(), HI()>, long_grid(p), dkv_lds_bytes<DHT()>(p.T, RAG()),
+                  st, p, "nstl_attn_bwd long dkv", LNT);
+  });
 }
-
-}  // namespace nstl

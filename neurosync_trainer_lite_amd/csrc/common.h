@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define NSTL_DEV __device__ __forceinline__
 
 typedef __bf16 bf16;
@@ -239,3 +241,11 @@ NSTL_DEV int xcd_remap(int bid, int nwg) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
 }
 
+// Host: a run-time int as the std::integral_constant argument of a generic lambda,
+// the first of VS... that equals it.  False (nothing called) when none does.
+namespace nstl {
+template <int... VS, class F>
+bool with_const(int v, F&& f) {
+  return (... || (v == VS ? (f(std::integral_constant<int, VS>{}), true) : false));
+}
+}  // namespace nstl

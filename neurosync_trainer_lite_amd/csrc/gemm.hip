@@ -1138,7 +1138,7 @@ int launch_ring(const nstl_gemm_args* a, const GemmParams& p, int em, int splits
   const int nt = ((a->M + BIG - 1) / BIG) * ((a->N + BIG - 1) / BIG);
   const dim3 grid(nt, splits), block(BIG_NT);
   if (a->dtype == NSTL_FP8) {
-    nstl::with_em<EM_BF16, EM_RELU_DROP, EM_ROPE, EM_DRELU, EM_F32>(em, [&](auto EM) {
+    nstl::with_const<EM_BF16, EM_RELU_DROP, EM_ROPE, EM_DRELU, EM_F32>(em, [&](auto EM) {
       hipLaunchKernelGGL((gemm256f8_kernel<decltype(EM)::value>), grid, block, 0, st, p);
     });
     NSTL_LAUNCH_CHECK("nstl_gemm (FP8)");
@@ -1147,7 +1147,7 @@ int launch_ring(const nstl_gemm_args* a, const GemmParams& p, int em, int splits
     return 0;
   }
   nstl::with_layout(a->a_kmajor, a->b_kmajor, [&](auto AK, auto BKM) {
-    nstl::with_em<EM_GENERIC, EM_BF16, EM_RELU_DROP, EM_ROPE, EM_DRELU, EM_F32, EM_WS>(em, [&](auto EM) {
+    nstl::with_const<EM_GENERIC, EM_BF16, EM_RELU_DROP, EM_ROPE, EM_DRELU, EM_F32, EM_WS>(em, [&](auto EM) {
       hipLaunchKernelGGL((gemm256r_kernel<decltype(AK)::value, decltype(BKM)::value, decltype(EM)::value>), grid, block,
                          0, st, p);
     });

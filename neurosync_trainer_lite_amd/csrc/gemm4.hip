@@ -93,7 +93,7 @@ template <bool GROUPED, bool SK, int R3>
 bool launch_as(const nstl::Gemm4Route& r, dim3 grid, hipStream_t st, const g4::GroupParams& gp) {
   bool done = false;
   nstl::with_layout(r.ak, r.bk, [&](auto AK, auto BKM) {
-    nstl::with_em<g4::EM_BF16, g4::EM_RELU_DROP, g4::EM_ROPE, g4::EM_DRELU, g4::EM_F32>(r.em, [&](auto EM) {
+    nstl::with_const<g4::EM_BF16, g4::EM_RELU_DROP, g4::EM_ROPE, g4::EM_DRELU, g4::EM_F32>(r.em, [&](auto EM) {
       constexpr bool ak = decltype(AK)::value, bkm = decltype(BKM)::value;
       constexpr int em = decltype(EM)::value;
       if constexpr (nstl::g4_has(ak, bkm, em, GROUPED, SK, R3)) {
@@ -112,7 +112,7 @@ int nstl::gemm4_launch(g4::GroupParams& gp, const Gemm4Route& r, hipStream_t st)
   const dim3 grid(tiles < r.G ? tiles : r.G);
   bool done;
   if (r.f8) {
-    done = with_em<g4::EM_BF16, g4::EM_RELU_DROP, g4::EM_ROPE, g4::EM_DRELU>(r.em, [&](auto EM) {
+    done = with_const<g4::EM_BF16, g4::EM_RELU_DROP, g4::EM_ROPE, g4::EM_DRELU>(r.em, [&](auto EM) {
       hipLaunchKernelGGL((g4::gemm4f8_kernel<decltype(EM)::value>), grid, dim3(g4::NT), 0, st, gp);
     });
   } else {

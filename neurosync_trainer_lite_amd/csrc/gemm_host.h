@@ -16,13 +16,6 @@ void with_layout(bool ak, bool bk, F&& f) {
   else f(std::false_type{}, std::true_type{});
 }
 
-// Runtime `em` as the std::integral_constant argument of a generic lambda: the
-// first of EMS... that equals it.  False (nothing called) when none does.
-template <int... EMS, class F>
-bool with_em(int em, F&& f) {
-  return ((em == EMS ? (f(std::integral_constant<int, EMS>{}), true) : false) || ...);
-}
-
 // The gemm4_kernel<AK, BKM, EM, GROUPED, 0, SK, R3> instantiations that exist;
 // routing asks it at run time, the launch at compile time.  Forward and dX (A
 // K-major) take every epilogue, RoPE only with a K-major B and never R3; NN (the
