@@ -40,6 +40,8 @@ enum {
 /* C[i,j] = alpha * sum_r A(i,r) B(j,r)  (+ beta*C, + epilogue).
  *   a_kmajor: A stored [M][K] (r contiguous) else [K][M];
  *   b_kmajor: B stored [N][K] else [K][N].
+ *   A K-major row is read in 16-byte chunks: lda / ldb >= K rounded up to a chunk
+ *   (the last chunk must be readable); what it holds past K does not enter the sum.
  * Replaces nn.Linear forward/backward GEMMs: utils/model.py:113-115,138
  * (MultiHeadAttention q/k/v/out_linear), :154,:157 (FeedForwardNetwork),
  * :216/:224 (Encoder.embedding), :242/:251 (Decoder.fc_output); the bias+ReLU+
@@ -291,8 +293,19 @@ int nstl_rope(int in_dtype, const void* in, int64_t in_ld, int out_dtype, void* 
 
 /* Fused Loss forward + backward.  Replaces Loss.forward (utils/model.py:278-291)
  * and its autograd backward.  loss_out[0..3] = total, rec, temp, dir.
- * 2 <= T <= 4096, F <= 64: clips up to 256 frames are staged whole in LDS, longer
- * ones in time chunks with one frame of halo (same sums, same normalisers). */
+ * 2 <= T <= 4096 and delta > 0 always; every ld >= F.  One workgroup per sequence
+ * stages the clip in one of two LDS tiles (f32, odd row stride):
+ *   tile             F          whole clip up to   longer clips: chunks of      flags
+ *   [256][64 + 1]    1..64      256 frames         254 frames + 2 halo frames   any
+ *   [128][128 + 1]   65..128    128 frames         126 frames + 2 halo frames   NSTL_LOSS_WIDE_OK
+ * A chunk carries one frame of halo on either side (same sums, same normalisers as
+ * the whole-clip form).  NSTL_LOSS_CHUNKED=1 in the environment takes the chunked
+ * form of either tile also where the whole clip fits (tests).
+ * flags == 0 is the behaviour of version 5 for every shape: F > 64 is rejected.
+ * With NSTL_LOSS_WIDE_OK a call with 64 < F <= 128 takes the wide tile; calls with
+ * F <= 64 run the same kernels with the flag set or not.  F > 128, F <= 0, T outside
+ * [2, 4096], an ld < F and delta <= 0 are rejected whatever the flags are. */
+#define NSTL_LOSS_WIDE_OK 1u /* flags bit 0: 64 < F <= 128 may take the [128][129] tile */
 typedef struct nstl_loss_args {
   int B, T, F;
   const float* pred; int64_t pred_ld;
@@ -302,6 +315,7 @@ typedef struct nstl_loss_args {
   void* dpred; int dpred_dtype; int64_t dpred_ld;   /* columns F..dpred_ld-1 zeroed */
   float* partial;          /* [B][4] scratch */
   float* loss_out;         /* [4] */
+  unsigned flags;          /* NSTL_LOSS_*; 0: the limits of version 5 for every shape */
 } nstl_loss_args;
 int nstl_loss_fwd_bwd(const nstl_loss_args* args, void* stream);
 
@@ -409,7 +423,9 @@ const char* nstl_last_error_string(void);
    4: NSTL_ATTN_DHANY_OK (streaming MFMA attention at every head_dim % 8 == 0 up to
       128); no struct changed.
    5: nstl_attn_route_describe; the attention size queries answer 0 for arguments the
-      entry points reject for their shape. */
+      entry points reject for their shape.
+   6: nstl_loss_args.flags, NSTL_LOSS_WIDE_OK (the fused loss at 64 < F <= 128),
+      NSTL_K_LOSS_WIDE. */
 int nstl_version(void);
 
 /* Launch counters by kernel family, process-wide (host side, counted at each
@@ -436,6 +452,7 @@ enum {
   NSTL_K_GEMM4F8,            /* fp8 GEMM launches on the 4-wave persistent kernel (the rest: NSTL_K_GEMM_FP8) */
   NSTL_K_ATTN_FWD_LONG,      /* streaming MFMA attention forward (the table above nstl_attn_args) */
   NSTL_K_ATTN_BWD_LONG,      /*   ... its backward (dQ + dK/dV kernel pair) */
+  NSTL_K_LOSS_WIDE,          /* fused loss launches on the [128][129] tile (64 < F <= 128), whole-clip or chunked */
   NSTL_K_COUNT
 };
 /* Copy-engine ZeRO-1 (parallel.ShardPusher; replaces the reference's gather of

@@ -93,8 +93,11 @@ class LossArgs(ctypes.Structure):
         ("pred", _vp), ("pred_ld", _i64), ("trg", _vp), ("trg_ld", _i64),
         ("delta", _f32), ("w1", _f32), ("w2", _f32), ("w3", _f32), ("grad_scale", _f32),
         ("dpred", _vp), ("dpred_dtype", _i32), ("dpred_ld", _i64),
-        ("partial", _vp), ("loss_out", _vp),
+        ("partial", _vp), ("loss_out", _vp), ("flags", ctypes.c_uint),
     ]
+
+
+LOSS_WIDE_OK = 1  # NSTL_LOSS_WIDE_OK
 
 
 class AdamArgs(ctypes.Structure):
@@ -133,7 +136,7 @@ IPC_HANDLE_BYTES = 64
 KERNEL_COUNT_NAMES = ["gemm128", "gemm_ring", "gemm_ring_tiles", "gemm_group", "gemm_group_tiles",
                       "gemm_splitk_reduce", "gemm_fp8", "attn_fwd", "attn_fwd_generic", "attn_bwd_fused",
                       "attn_bwd_split", "attn_bwd_generic", "gemm4", "gemm4_tiles", "gemm4_sk", "gemm_fp8_rope", "gemm4_fp8",
-                      "attn_fwd_long", "attn_bwd_long"]
+                      "attn_fwd_long", "attn_bwd_long", "loss_wide"]
 
 _lib = None
 

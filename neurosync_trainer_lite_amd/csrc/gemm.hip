@@ -218,6 +218,16 @@ struct Stager {
         reg[s] = *(const uint4*)(base + e * (int64_t)sizeof(T));
       else
         reg[s] = make_uint4(0, 0, 0, 0);
+      // the chunk that straddles the end of the reduction extent: what lies past K is
+      // read (it must be readable up to ld) but counts as zero whatever it holds
+      if (KMAJ && ok && gk + EPC > K) {
+        const int nb = (K - gk) * (int)sizeof(T);  // live bytes of the chunk, 1..15
+        auto keep = [nb](uint32_t v, int w) {
+          const int b = nb - 4 * w;
+          return b >= 4 ? v : (b <= 0 ? 0u : v & ((1u << (8 * b)) - 1u));
+        };
+        reg[s] = make_uint4(keep(reg[s].x, 0), keep(reg[s].y, 1), keep(reg[s].z, 2), keep(reg[s].w, 3));
+      }
     }
   }
   NSTL_DEV void store(char* img) {
@@ -1191,7 +1201,8 @@ int make_params(const nstl_gemm_args* a, GemmParams& p) {
                  "nstl_gemm: A and B must be 16-byte aligned");
   NSTL_CHECK_ARG(a->lda % vec == 0 && a->ldb % vec == 0, "nstl_gemm: lda/ldb must be multiples of %d", vec);
   // K-major rows are read in 16-byte chunks: the reduction extent is rounded up to
-  // a chunk and must be readable (zero-padded) up to lda/ldb.
+  // a chunk and must be readable up to lda/ldb (the 128 kernel's Stager masks what a
+  // chunk holds past K; the other kernels take whole-chunk K only).
   NSTL_CHECK_ARG(!a->a_kmajor || a->lda >= ((a->K + vec - 1) / vec) * vec, "nstl_gemm: lda < K");
   NSTL_CHECK_ARG(!a->b_kmajor || a->ldb >= ((a->K + vec - 1) / vec) * vec, "nstl_gemm: ldb < K");
   NSTL_CHECK_ARG(a->a_kmajor || a->lda >= ((a->M + vec - 1) / vec) * vec, "nstl_gemm: lda < M");

@@ -19,7 +19,7 @@ namespace {
 // 16 waves per sequence: the per-step cosine chain (3 wave reductions per step)
 // runs T/16 steps deep instead of T/4 (58 -> ~20 us at B=128, T=128)
 constexpr int NT = 1024;
-constexpr int TMAX = 256, FMAX = 64;
+constexpr int TMAX_NARROW = 256, FMAX_NARROW = 64, TMAX_WIDE = 128, FMAX_WIDE = 128;  // the two tiles <FMAX, TMAX>
 
 struct LossParams {
   int B, T, F;
@@ -30,7 +30,7 @@ struct LossParams {
   float* partial; float* out;
 };
 
-__global__ __launch_bounds__(NT) void loss_kernel(LossParams p) {
+template <int FMAX, int TMAX> __global__ __launch_bounds__(NT) void loss_kernel(LossParams p) {
   __shared__ float P[TMAX][FMAX + 1];
   __shared__ float Y[TMAX][FMAX + 1];
   // per-step scalars: 1/(|dp|+eps), 1/(|dy|+eps), cos_t, |dp|
@@ -124,15 +124,15 @@ __global__ __launch_bounds__(NT) void loss_kernel(LossParams p) {
   }
 }
 
-// Clips longer than TMAX frames: the same sums over time chunks of CH frames, each
+// Clips longer than TMAX frames: the same sums over time chunks of CH = TMAX - 2 frames, each
 // staged with one frame of halo on either side (the first differences, and the
 // cosine gradient's t-1 and t terms, reach one frame across a chunk edge).  The
 // step s = t0 - 1 that straddles two chunks is evaluated in both with identical
 // values, and counted in the cosine sum by the chunk that owns frame s.
-constexpr int CH = TMAX - 2;
+template <int TMAX> constexpr int CH = TMAX - 2;  // frames a chunk owns: 254 (narrow tile), 126 (wide tile)
 constexpr int TMAX_LONG = 4096;
 
-__global__ __launch_bounds__(NT) void loss_long_kernel(LossParams p) {
+template <int FMAX, int TMAX> __global__ __launch_bounds__(NT) void loss_long_kernel(LossParams p) {
   __shared__ float P[TMAX][FMAX + 1];
   __shared__ float Y[TMAX][FMAX + 1];
   __shared__ float s_inp[TMAX], s_iny[TMAX], s_cos[TMAX], s_np[TMAX];
@@ -144,8 +144,8 @@ __global__ __launch_bounds__(NT) void loss_long_kernel(LossParams p) {
   const float n_dir = (float)p.B * (T - 1);
   const int ldd = (int)p.dpred_ld;
   float cos_acc = 0.f, rec_acc = 0.f, tmp_acc = 0.f;
-  for (int t0 = 0; t0 < T; t0 += CH) {
-    const int t1 = min(T, t0 + CH);                       // frames this chunk owns: [t0, t1)
+  for (int t0 = 0; t0 < T; t0 += CH<TMAX>) {
+    const int t1 = min(T, t0 + CH<TMAX>);                      // frames this chunk owns: [t0, t1)
     const int lo = max(t0 - 1, 0), hi = min(t1 + 1, T);  // staged frames [lo, hi), row = t - lo
     const int n = hi - lo;
     for (int e = tid; e < n * F; e += NT) {
@@ -251,11 +251,20 @@ __global__ void loss_final(LossParams p) {
 }
 }  // namespace
 
+// Two LDS tiles, both with an odd row stride and one workgroup per CU (160 KiB of LDS):
+//   narrow  F <= 64:   P, Y [256][65]  f32 = 133,120 B; 137,408 B with the step scalars and red
+//   wide    F <= 128:  P, Y [128][129] f32 = 132,096 B; 134,336 B likewise (NSTL_LOSS_WIDE_OK)
+// Both kernels are templates on the tile.  The per-step loops stride f += 64, so a lane
+// of the wide form owns up to two elements of each step sum; the chunked form stages at
+// most CH + 2 = TMAX rows.  Everything a tile needs (F <= FMAX, the T range) is checked
+// here, and the chunk loop's bound comes from T alone.
 extern "C" int nstl_loss_fwd_bwd(const nstl_loss_args* a, void* stream) {
   NSTL_CHECK_ARG(a != nullptr, "nstl_loss: null args");
-  NSTL_CHECK_ARG(a->B > 0 && a->T >= 2 && a->T <= TMAX_LONG && a->F > 0 && a->F <= FMAX,
+  // flags 0: the limits of version 5; NSTL_LOSS_WIDE_OK: 64 < F <= 128 takes the wide tile
+  const int fmax = (a->flags & NSTL_LOSS_WIDE_OK) ? FMAX_WIDE : FMAX_NARROW;
+  NSTL_CHECK_ARG(a->B > 0 && a->T >= 2 && a->T <= TMAX_LONG && a->F > 0 && a->F <= fmax,
                  "nstl_loss: shape B=%d T=%d F=%d unsupported (T in [2,%d], F <= %d)", a->B, a->T, a->F, TMAX_LONG,
-                 FMAX);
+                 fmax);
   NSTL_CHECK_ARG(a->pred && a->trg && a->dpred && a->partial && a->loss_out, "nstl_loss: null tensor");
   NSTL_CHECK_ARG(a->dpred_ld >= a->F && a->pred_ld >= a->F && a->trg_ld >= a->F, "nstl_loss: ld < F");
   NSTL_CHECK_ARG(a->delta > 0.f, "nstl_loss: delta must be > 0");
@@ -269,9 +278,21 @@ extern "C" int nstl_loss_fwd_bwd(const nstl_loss_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   // NSTL_LOSS_CHUNKED=1: the chunked kernel also where the whole clip fits (tests; read per call)
   const char* e = getenv("NSTL_LOSS_CHUNKED");
-  if (a->T > TMAX || (e && e[0] == '1')) hipLaunchKernelGGL(loss_long_kernel, dim3(a->B), dim3(NT), 0, st, p);
-  else hipLaunchKernelGGL(loss_kernel, dim3(a->B), dim3(NT), 0, st, p);
-  NSTL_LAUNCH_CHECK("nstl_loss_fwd_bwd");
+  const bool forced = e && e[0] == '1';
+  if (a->F > FMAX_NARROW) {  // only with NSTL_LOSS_WIDE_OK (checked above); F <= FMAX_WIDE
+    if (a->T > TMAX_WIDE || forced)
+      hipLaunchKernelGGL((loss_long_kernel<FMAX_WIDE, TMAX_WIDE>), dim3(a->B), dim3(NT), 0, st, p);
+    else
+      hipLaunchKernelGGL((loss_kernel<FMAX_WIDE, TMAX_WIDE>), dim3(a->B), dim3(NT), 0, st, p);
+    NSTL_LAUNCH_CHECK("nstl_loss_fwd_bwd");
+    nstl::count(NSTL_K_LOSS_WIDE);
+  } else {
+    if (a->T > TMAX_NARROW || forced)
+      hipLaunchKernelGGL((loss_long_kernel<FMAX_NARROW, TMAX_NARROW>), dim3(a->B), dim3(NT), 0, st, p);
+    else
+      hipLaunchKernelGGL((loss_kernel<FMAX_NARROW, TMAX_NARROW>), dim3(a->B), dim3(NT), 0, st, p);
+    NSTL_LAUNCH_CHECK("nstl_loss_fwd_bwd");
+  }
   hipLaunchKernelGGL(loss_final, dim3(1), dim3(64), 0, st, p);
   NSTL_LAUNCH_CHECK("nstl_loss_fwd_bwd final");
   return 0;

@@ -86,7 +86,7 @@ class AudioFacialDataset(Dataset):
         self.frame_rate = config['frame_rate']
         self.micro_batch_size = config['micro_batch_size']
         self.processed_folders = set()
-        self.clips = []   # [(audio f32 [N, 256], facial f32 [N, 61])]
+        self.clips = []   # [(audio f32 [N, 256], facial f32 [N, C])], C the clip's own column count (61, or 68 with emotions)
         self.index = []   # [(clip, start, is_tail)]
         self.pin = torch.cuda.is_available()
         for audio_features, facial_data in load_data(self.root_dir, self.sr, self.processed_folders,
@@ -120,6 +120,8 @@ class AudioFacialDataset(Dataset):
         """A whole batch (torch DataLoader batched fetch): windows copied into one
         pinned (src, trg) pair, in index order."""
         w = self.micro_batch_size
+        # the widths are the first window's clip's own (61 target columns, or 68 with the emotion
+        # values); an empty batch has no clip to ask and keeps the default layout
         a0, f0 = self.clips[self.index[indices[0]][0]] if len(indices) else (np.zeros((0, 256)), np.zeros((0, 61)))
         src = torch.empty((len(indices), w, a0.shape[1]), dtype=torch.float32, pin_memory=self.pin)
         trg = torch.empty((len(indices), w, f0.shape[1]), dtype=torch.float32, pin_memory=self.pin)
@@ -154,7 +156,7 @@ class AudioFacialDataset(Dataset):
 
 
 class _Batch(list):
-    """(src [B, T, 256], trg [B, T, 61]) as fetched by __getitems__.  It is also
+    """(src [B, T, 256], trg [B, T, C], C the clips' own target column count) as fetched by __getitems__.  It is also
     the list of per-window (src_i, trg_i) pairs (views of the pinned batch), so a
     DataLoader with torch's default_collate (or any collate that takes a list of
     samples) still works; AudioFacialDataset.collate_fn takes the pinned tensors

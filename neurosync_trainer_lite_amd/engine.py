@@ -133,7 +133,7 @@ class _Buffers:
             self.dkv_all = e(M, nl * 2 * D) if eng.dmem_concat else None
             self.dh = e(M, Fd)
             self.demb = e(M, D)
-            self.dpred = torch.zeros(M, 64, dtype=dt, device=dev)
+            self.dpred = torch.zeros(M, eng.head_ld, dtype=dt, device=dev)
             self.dsum = e(B * eng.H * T, dtype=f32)  # attention backward rowsum(dO * O)
             # attention backward: per-(batch, 128 rows) column sums of dq | dk | dv (bias grads)
             # (two: a decoder layer's cross and self attention reduce in one batch)
@@ -187,6 +187,8 @@ class Seq2SeqEngine:
         self.D = enc.embedding.out_features
         self.in_dim = enc.embedding.in_features
         self.out_dim = dec.fc_output.out_features
+        # padded width of the output head's pred / dpred rows: 64 up to output_dim 64, 128 above
+        self.head_ld = 64 if self.out_dim <= 64 else 128
         self.L = len(enc.transformer_encoder)
         self.H = enc.transformer_encoder[0].self_attn.num_heads
         self.dh = self.D // self.H
@@ -262,8 +264,8 @@ class Seq2SeqEngine:
             raise ValueError("head_dim must be a multiple of 8 up to 512 (hidden_dim=%d, num_heads=%d)" % (D, H))
         if D % 128 or D > 2048:
             raise ValueError("hidden_dim must be a multiple of 128 and <= 2048 (got %d)" % D)
-        if self.out_dim > 64:
-            raise ValueError("output_dim must be <= 64 (got %d)" % self.out_dim)
+        if self.out_dim > 128:
+            raise ValueError("output_dim must be <= 128 (got %d)" % self.out_dim)
         if self.in_dim % 8:
             raise ValueError("input_dim must be a multiple of 8 (got %d)" % self.in_dim)
 
@@ -1062,7 +1064,7 @@ class Seq2SeqEngine:
         return bb.mem
 
     def decode(self, bb, mem, T, xdec0=None):
-        """Decoder forward from `mem`; returns pred f32 [M, 64] (first out_dim valid)."""
+        """Decoder forward from `mem`; returns pred f32 [M, head_ld] (first out_dim valid)."""
         if xdec0 is None:
             K.rope(mem, self.D, bb.xdec0, self.D, bb.M, self.D, *self.rope(T, self.D), T, self.D, stream=self.st)
             xdec0 = bb.xdec0
@@ -1072,7 +1074,7 @@ class Seq2SeqEngine:
         for l in range(self.L):
             x = self._dec_layer(bb, l, x, mem, T)
         self._ln(None, x, bb.xf, bb.decf_stats, "decoder.layer_norm", 0, (0, 0), None)
-        pred = torch.empty(bb.M, 64, dtype=torch.float32, device=self.device)
+        pred = torch.empty(bb.M, self.head_ld, dtype=torch.float32, device=self.device)
         self.await_stage("head")
         self._gemm_fwd(bb.xf, "decoder.fc_output.weight", pred, K.EPI_BIAS)
         return pred
@@ -1124,7 +1126,8 @@ class Seq2SeqEngine:
         dres = bb.dres
         # head: pred = xf W^T + b
         g = grad_pred.reshape(M, self.out_dim)
-        K.copy2d(g, g.stride(0), bb.dpred, 64, M, self.out_dim, 64, scale=self.grad_scale_t, stream=self.st)
+        K.copy2d(g, g.stride(0), bb.dpred, self.head_ld, M, self.out_dim, self.head_ld, scale=self.grad_scale_t,
+                 stream=self.st)
         red = self.grad_reducer
         if red is not None:
             red.begin(self.grads_fresh)
@@ -1132,7 +1135,7 @@ class Seq2SeqEngine:
         dpred = bb.dpred[:, :self.out_dim]
         self._dw(dpred, bb.xf, "decoder.fc_output.weight", 1, bf, ws)
         K.gemm(bb.dpred, self.w("decoder.fc_output.weight"), dres, M, D, self.out_dim, a_kmajor=True,
-               b_kmajor=False, lda=64, beta=0.0, stream=self.st)
+               b_kmajor=False, lda=self.head_ld, beta=0.0, stream=self.st)
         x_last = bb.layer(bb.d_x3, L - 1)
         self._ln_bwd(x_last, bb.decf_stats, "decoder.layer_norm", dres, dres, None, 0, (0, 0), bf)
         ready("decoder.layer_norm.bias")

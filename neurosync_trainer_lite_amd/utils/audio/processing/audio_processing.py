@@ -72,7 +72,9 @@ def chunk_plan(num_frames, frame_length, overlap):
 
 
 def process_audio_features(audio_features, model, device, config):
-    """audio_processing.py:50-112 -> [num_frames, 61] (blendshapes / 100)."""
+    """audio_processing.py:50-112 -> [num_frames, output_dim]; only the first 61 columns
+    (blendshapes and head pose) are divided by 100, as in the reference: the emotion
+    columns of a 68-output model come back as the model gives them."""
     frame_length = config['frame_size']
     overlap = config.get('overlap', 16)
     num_features = audio_features.shape[1]

@@ -401,6 +401,7 @@ class _LossFunction(torch.autograd.Function):
         a.delta, a.w1, a.w2, a.w3, a.grad_scale = delta, w1, w2, w3, 1.0
         a.dpred, a.dpred_dtype, a.dpred_ld = dpred.data_ptr(), K.F32, F
         a.partial, a.loss_out = partial.data_ptr(), out.data_ptr()
+        a.flags = K.LOSS_WIDE_OK  # 64 < F <= 128 takes the wide tile; F > 128 raises the library's message
         K.loss_fwd_bwd(a)
         ctx.save_for_backward(dpred)
         ctx.parts = out
