@@ -415,6 +415,42 @@ int nstl_features_frames(int64_t n_samples, int sr);
 int nstl_cmvn_delta_reduce(const float* x, int ncoef, int F, float* out, int64_t ld_out, void* stream);
 int nstl_reduce_frame_pairs(const double* x, int F, int cols, float* out, int64_t ld_out, int col0, void* stream);
 
+/* Audio ingest after the host's WAV parse (utils/audio/load_audio.py: the reference's
+ * librosa.load resamples on the host, load_audio.py:18-21, and peak-normalises, :13-15).
+ * nstl_resample_poly: rational-ratio polyphase FIR resampler, f32 in and out, with the
+ * semantics of scipy.signal.resample_poly(x, up, down) at its defaults (window
+ * ('kaiser', 5.0), padtype 'constant').  With max_rate = max(up, down) and
+ * half = 10 max_rate, `taps` is the prototype
+ *   h = firwin(2 half + 1, 1 / max_rate, window=('kaiser', 5.0)) * up
+ * rounded to f32 (n_taps = 20 max_rate + 1 values on the device, without the zeros
+ * below).  pre = down - half % down zeros go in front of h (hp), rem = (half + pre) /
+ * down, n_out = ceil(n_in up / down) = nstl_resample_out_len, and for 0 <= m < n_out,
+ * t0 = (m + rem) down:
+ *   y[m] = sum of hp[k] x[(t0 - k) / up] over k == t0 (mod up), 0 <= k < len(hp),
+ * terms whose sample index falls outside [0, n_in) dropped; accumulated in f32 in
+ * ascending k by one thread per output, so a call repeats bit for bit.
+ * peak (optional, device float[1]): zeroed on `stream`, then max |y[m]| exactly, over
+ * the outputs that are not NaN (a NaN output is written to y but does not enter the
+ * maximum, where numpy's max would be NaN).
+ * Rejected before any launch: null args / x / taps / y, n_in < 1, up or down outside
+ * [1, 16384], n_taps != 20 max(up, down) + 1, n_out != nstl_resample_out_len,
+ * n_in up >= 2^62.  The tap table lives in LDS while it and a run's input span fit
+ * one workgroup's 64 KB; past that the same kernel reads taps (and, for strongly
+ * decimating ratios, samples) from global memory. */
+typedef struct nstl_resample_args {
+  const float* x; int64_t n_in;        /* input samples (device) */
+  int up, down;
+  const float* taps; int n_taps;       /* f32 prototype h (device), 20 max(up, down) + 1 */
+  float* y; int64_t n_out;             /* output samples (device), nstl_resample_out_len */
+  float* peak;                         /* optional device [1]: max |y| */
+} nstl_resample_args;
+int nstl_resample_poly(const nstl_resample_args* args, void* stream);
+/* ceil(n_in up / down); 0 for arguments nstl_resample_poly rejects.  Host arithmetic. */
+int64_t nstl_resample_out_len(int64_t n_in, int up, int down);
+/* y[i] = y[i] / peak[0] (IEEE division: numpy's y / m bit for bit) when peak[0] > 0,
+ * else y unchanged (load_audio.py:13-15).  peak: device float[1]. */
+int nstl_peak_normalise(float* y, int64_t n, const float* peak, void* stream);
+
 const char* nstl_last_error_string(void);
 /* ABI version: raised whenever a struct of this header changes size or layout, or
    a flag is added.
@@ -425,7 +461,9 @@ const char* nstl_last_error_string(void);
    5: nstl_attn_route_describe; the attention size queries answer 0 for arguments the
       entry points reject for their shape.
    6: nstl_loss_args.flags, NSTL_LOSS_WIDE_OK (the fused loss at 64 < F <= 128),
-      NSTL_K_LOSS_WIDE. */
+      NSTL_K_LOSS_WIDE.
+   7: nstl_resample_poly, nstl_resample_out_len, nstl_peak_normalise (audio ingest on
+      the device); no struct changed. */
 int nstl_version(void);
 
 /* Launch counters by kernel family, process-wide (host side, counted at each

@@ -116,6 +116,12 @@ class ReduceJob(ctypes.Structure):
 
 REDUCE_BATCH_MAX = 16
 
+
+class ResampleArgs(ctypes.Structure):
+    _fields_ = [("x", _vp), ("n_in", _i64), ("up", _i32), ("down", _i32), ("taps", _vp), ("n_taps", _i32),
+                ("y", _vp), ("n_out", _i64), ("peak", _vp)]
+
+
 # every symbol include/nstl.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "nstl_gemm", "nstl_gemm_grouped", "nstl_gemm_colsum_rows", "nstl_gemm_relu_mask_words",
@@ -129,6 +135,7 @@ EXPORTS = [
     "nstl_version", "nstl_fp8_quant_rows", "nstl_fp8_quant_cols", "nstl_kernel_counts", "nstl_kernel_counts_reset",
     "nstl_cmvn_delta_reduce", "nstl_reduce_frame_pairs", "nstl_transpose_bf16", "nstl_stream_cus", "nstl_mask_grid",
     "nstl_ipc_handle", "nstl_ipc_open", "nstl_ipc_close", "nstl_copy_engine", "nstl_shard_sum",
+    "nstl_resample_poly", "nstl_resample_out_len", "nstl_peak_normalise",
 ]
 IPC_HANDLE_BYTES = 64
 
@@ -209,6 +216,10 @@ def lib():
         L.nstl_ipc_close.argtypes = [_vp]
         L.nstl_copy_engine.argtypes = [_vp, _vp, _i64, _vp]
         L.nstl_shard_sum.argtypes = [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp]
+        L.nstl_resample_poly.argtypes = [P(ResampleArgs), _vp]
+        L.nstl_resample_out_len.argtypes = [_i64, _i32, _i32]
+        L.nstl_resample_out_len.restype = _i64
+        L.nstl_peak_normalise.argtypes = [_vp, _i64, _vp, _vp]
         _lib = L
     return _lib
 
@@ -680,3 +691,33 @@ def features(y, sr, out, workspace, stream=None):
     check(lib().nstl_features(y.data_ptr(), y.numel(), sr, out.data_ptr(), out.stride(0), out.shape[0],
                               workspace.data_ptr(), workspace.numel() * workspace.element_size(),
                               stream if stream is not None else stream_of()), "nstl_features")
+
+
+def resample_out_len(n_in, up, down):
+    """ceil(n_in up / down), 0 for arguments nstl_resample_poly rejects (host arithmetic)."""
+    return lib().nstl_resample_out_len(n_in, up, down)
+
+
+def resample_poly(x, up, down, taps, y, peak=None, stream=None):
+    """x f32 [n_in] -> y f32 [resample_out_len] with scipy.signal.resample_poly's default
+    filter (nstl_resample_poly); taps: the f32 prototype h on the device, 20 max(up, down)
+    + 1 values; peak: optional f32 [1], receives max |y|.  All on one device."""
+    for name, t in (("x", x), ("taps", taps), ("y", y), ("peak", peak)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("nstl_resample_poly: %s must be a contiguous float32 tensor" % name)
+    a = ResampleArgs(x.data_ptr(), x.numel(), up, down, taps.data_ptr(), taps.numel(), y.data_ptr(), y.numel(),
+                     ptr(peak))
+    _check_side(peak, 1, "nstl_resample_poly peak [1]")
+    check(lib().nstl_resample_poly(ctypes.byref(a), stream if stream is not None else stream_of()),
+          "nstl_resample_poly")
+
+
+def peak_normalise(y, peak, n=None, stream=None):
+    """y[:n] /= peak[0] in place when peak[0] > 0 (nstl_peak_normalise); y, peak f32 on the device."""
+    n = y.numel() if n is None else n
+    if y.dtype != torch.float32 or peak.dtype != torch.float32 or not y.is_contiguous():
+        raise TypeError("nstl_peak_normalise: contiguous float32 tensors")
+    _need(y, n - 1, "nstl_peak_normalise y [n]")
+    _check_side(peak, 1, "nstl_peak_normalise peak [1]")
+    check(lib().nstl_peak_normalise(y.data_ptr(), n, peak.data_ptr(), stream if stream is not None else stream_of()),
+          "nstl_peak_normalise")

@@ -2,7 +2,11 @@
 same defaults.  Hidden keys the reference reads with defaults are listed explicitly:
 ``use_amp`` (train.py:25; here: bf16 compute when True, fp32 parity mode when False)
 and ``overlap`` (audio_processing.py:53).  ``use_fp8`` (not a reference key, default
-False) selects BASELINE config C5's fp8 q/k/v and FFN forward GEMMs.  ``num_gpus`` is no longer capped at 4: the
+False) selects BASELINE config C5's fp8 q/k/v and FFN forward GEMMs.
+``device_audio_ingest`` (not a reference key, default False): the dataset build
+(dataset/data_processing.collect_features) and the per-epoch validation clip resample
+and peak-normalise their audio on the GPU (``extract_audio_features(...,
+device_ingest=True)``) instead of with scipy on the host.  ``num_gpus`` is no longer capped at 4: the
 data-parallel path is one process per GPU (torchrun), see parallel.py."""
 import os
 import shutil
@@ -41,4 +45,5 @@ training_config = {
     'checkpoint_path': r"out/checkpoints/checkpoint.pth",
     'use_amp': True,
     'overlap': 16,
+    'device_audio_ingest': False,
 }

@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pandas as pd
 
+from ..config import training_config
 from ..utils.audio.extraction.extract_features import extract_audio_features
 
 COLUMNS_TO_DROP = ['Timecode', 'BlendshapeCount']
@@ -125,7 +126,10 @@ def collect_features(audio_path, audio_features_csv_path, facial_csv_path, sr,
         audio_features = pd.read_csv(audio_features_csv_path).values
     else:
         print(f"Extracting audio features from {audio_path}")
-        audio_features, _ = extract_audio_features(audio_path, sr)
+        if training_config.get('device_audio_ingest', False):  # resample on the GPU (config.py)
+            audio_features, _ = extract_audio_features(audio_path, sr, device_ingest=True)
+        else:
+            audio_features, _ = extract_audio_features(audio_path, sr)
         if audio_features is not None:
             pd.DataFrame(audio_features).to_csv(audio_features_csv_path, index=False)
             print(f"Audio features saved to {audio_features_csv_path}")

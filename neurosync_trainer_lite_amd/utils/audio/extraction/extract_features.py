@@ -11,7 +11,8 @@ import numpy as np
 import torch
 
 from .... import _hip as K
-from ..load_audio import load_and_preprocess_audio, load_audio_from_bytes
+from ..load_audio import (load_and_preprocess_audio, load_and_preprocess_audio_device, load_audio_from_bytes,
+                          load_audio_from_bytes_device)
 
 N_FEATURES = 256
 MIN_FRAMES = 9
@@ -41,8 +42,31 @@ def extract_audio_features_device(y, sr=88200, device=None, stream=None):
     return out
 
 
-def extract_audio_features(audio_input, sr=88200, from_bytes=False):
-    """extract_features.py:6-24."""
+def audio_features_from_device_ingest(audio_input, sr=88200, from_bytes=False, device=None, stream=None):
+    """Bytes or a path -> (f32 [F60, 256] features, audio), both device tensors, with the
+    resampling and peak normalisation on the GPU (load_audio's ``*_device`` loaders);
+    (None, None) for a clip under 9 frames."""
+    if from_bytes:
+        y, sr = load_audio_from_bytes_device(audio_input, sr, device=device, stream=stream)
+    else:
+        y, sr = load_and_preprocess_audio_device(audio_input, sr, device=device, stream=stream)
+    frame_length, hop = frame_params(sr)
+    num_frames = (len(y) - frame_length) // hop + 1
+    if num_frames < MIN_FRAMES:
+        print(f"Audio file is too short: {num_frames} frames, required: {MIN_FRAMES} frames")
+        return None, None
+    return extract_audio_features_device(y, sr, device=y.device, stream=stream), y
+
+
+def extract_audio_features(audio_input, sr=88200, from_bytes=False, device_ingest=False):
+    """extract_features.py:6-24.  device_ingest=True (not a reference argument): clips at
+    another sample rate are resampled on the GPU instead of by scipy on the host; the
+    return value keeps its form."""
+    if device_ingest:
+        feats, y = audio_features_from_device_ingest(audio_input, sr, from_bytes)
+        if feats is None:
+            return None, None
+        return feats.double().cpu().numpy(), y.cpu().numpy()
     if from_bytes:
         y, sr = load_audio_from_bytes(audio_input, sr)
     else:

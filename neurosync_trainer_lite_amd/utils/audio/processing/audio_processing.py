@@ -100,6 +100,65 @@ def process_audio_features(audio_features, model, device, config):
     return final
 
 
+def _reflect_rows(start, end, frame_length):
+    """Feature rows of one chunk after pad_audio_chunk: rows start..end-1, then the last
+    frame_length - (end - start) rows of numpy's 'reflect' padding of that chunk."""
+    n = end - start
+    idx = np.arange(frame_length)
+    if n < frame_length:
+        if n == 1:
+            idx[:] = 0
+        else:
+            period = 2 * (n - 1)
+            idx = idx % period
+            idx = np.where(idx >= n, period - idx, idx)
+    return start + idx
+
+
+def _decode_batch_device(feats, rows, model):
+    """feats f32 [F, C] on the device, rows int64 [chunks, frame_length] on the host ->
+    decoded chunks [chunks, frame_length, out] on the host: one gather on the device, the
+    batched forwards of _decode_batch, one copy back."""
+    rows = torch.as_tensor(rows, device=feats.device)
+    outs = []
+    with torch.no_grad():
+        for i in range(0, rows.shape[0], MAX_CHUNKS_PER_FORWARD):
+            src = feats[rows[i:i + MAX_CHUNKS_PER_FORWARD]]
+            outs.append(model.decoder(model.encoder(src)))
+    return torch.cat(outs, dim=0).cpu().numpy()
+
+
+def process_audio_features_device(audio_features, model, config):
+    """process_audio_features for features that are already on the model's device (f32
+    tensor [num_frames, 256]): the same chunk plan and reflect padding as one index gather
+    there, the same batched forwards, the decoded chunks copied back once and blended on
+    the host by blend_chunks.  The features never visit the host; the result equals
+    process_audio_features(audio_features.double().cpu().numpy(), ...) bit for bit
+    (f32 -> f64 -> f32 is the identity)."""
+    frame_length = config['frame_size']
+    overlap = config.get('overlap', 16)
+    num_frames = audio_features.shape[0]
+    model.eval()
+    feats = audio_features.to(torch.float32).contiguous()
+    plan = chunk_plan(num_frames, frame_length, overlap)
+    decoded = _decode_batch_device(feats, np.stack([_reflect_rows(s, e, frame_length) for s, e in plan]), model)
+    all_decoded_outputs = []
+    for (s, e), out in zip(plan, decoded):
+        out = out[:e - s]
+        if all_decoded_outputs:
+            all_decoded_outputs.append(blend_chunks(all_decoded_outputs.pop(), out, overlap))
+        else:
+            all_decoded_outputs.append(out)
+    current_length = sum(len(c) for c in all_decoded_outputs)
+    if current_length < num_frames:
+        remaining = num_frames - current_length
+        rows = _reflect_rows(num_frames - remaining, num_frames, frame_length)[None]
+        all_decoded_outputs.append(_decode_batch_device(feats, rows, model)[0][:remaining])
+    final = ensure_2d(np.concatenate(all_decoded_outputs, axis=0)[:num_frames])
+    final[:, :61] /= 100
+    return final
+
+
 def zero_columns(data):
     columns_to_zero = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60]
     out = np.copy(data)

@@ -21,7 +21,10 @@ DIMENSION_LABELS = BLENDSHAPE_COLUMNS
 
 
 def generate_and_save_facial_data(epoch, audio_path, model, ground_truth_path, lock, device):
-    audio_features, _ = extract_audio_features(audio_path)
+    if training_config.get('device_audio_ingest', False):  # resample on the GPU (config.py)
+        audio_features, _ = extract_audio_features(audio_path, device_ingest=True)
+    else:
+        audio_features, _ = extract_audio_features(audio_path)
     generated_facial_data = process_audio_features(audio_features, model, device, training_config)
     base_dir = "dataset/validation_plots"
     stats_dir = os.path.join(base_dir, "stats")
