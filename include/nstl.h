@@ -226,13 +226,31 @@ int nstl_attn_route_describe(const nstl_attn_args* args, int backward, char* buf
  * Replaces `src = src + self.dropoutN(src2); src = self.normN(src)` at
  * utils/model.py:175-180, :198-207, the final LayerNorms :228-229, :249-250, and
  * (rot_out) the decoder-input GlobalPositionalEncoding at :246.
- * Width: D is a multiple of 128, 128 <= D <= 2048, in f32 and bf16; any other D
- * returns hipErrorInvalidValue.  The q8 / q8_scale copies exist at D = 128 / 256 /
- * 512 / 1024 only and are refused elsewhere.  At the other widths gamma and beta
- * must be 16-byte aligned and the rope tables 8-byte aligned.
- * Partials: the backward runs n_part blocks and block b writes row b of every
- * partial buffer, zeros when it finds no row.  n_part <= ceil(rows / 8) is legal at
- * every width (ceil(rows / 4) when D % 256 != 0); a larger n_part is refused. */
+ *
+ * Which kernels a call runs, in f32 and bf16 alike (D a multiple of 128, 128 <= D <= 2048;
+ * any other D returns hipErrorInvalidValue):
+ *
+ *   D                        forward            backward           h   q8    aligned tables
+ *   128                      wave V=2           wave V=2           4   -     -
+ *   256, 512, 1024           wave-il V=D/64     wave-il V=D/64     8   bf16  -
+ *   768                      wave-il V=12       wave-il V=12       8   -     -
+ *   1280, 1536, 1792, 2048   wave-il V=D/64     rowcoop            8   -     required
+ *   every other              rowcoop            rowcoop            4   -     required
+ *
+ * wave: one wave per row, a lane owns V = D / 64 contiguous columns.  wave-il: the same
+ * with the lane's columns in groups of G, 64 G apart; G = 8 when D % 512 == 0, else 4.
+ * rowcoop: a row split over ceil(D / 256) waves of a workgroup in the forward, over
+ * ceil(D / 512) in the backward, whose workgroup holds 8 / waves (rounded down) row groups.
+ * h: the backward runs n_part blocks and block b writes row b of every partial buffer,
+ * zeros when it finds no row; 0 < n_part <= ceil(rows / h), a larger n_part is refused
+ * (so n_part <= ceil(rows / 8) is legal at every width).
+ * q8: the q8 / q8_scale copies exist at D = 256 / 512 / 1024 in bf16 only, with q8_scale
+ * set, q8 16-byte aligned, ldq8 >= D a multiple of 16 and, in the backward, dbranch set;
+ * any other call that sets q8 is refused.
+ * aligned tables: gamma and beta must be 16-byte aligned and the rope tables 8-byte
+ * aligned, in both directions.
+ * Also refused: rows <= 0, n_masks outside 0..2, p_drop outside [0, 1), and rows * D
+ * past 2^33 with p_drop != 0 (the 32-bit dropout pair index). */
 typedef struct nstl_ln_args {
   int dtype; int rows, D;
   const void* x;           /* residual (dtype), may be NULL */
@@ -248,8 +266,8 @@ typedef struct nstl_ln_args {
   const float* dout;       /* f32 [rows][D] */
   float* ds;               /* f32 [rows][D] (may alias dout) */
   void* dbranch;           /* dtype: ds * masks / (1-p)^n_masks, may be NULL */
-  float* dgamma_part; float* dbeta_part; int n_part;   /* [n_part][D]; n_part <= ceil(rows/8)
-                                                          (rows/4 when D % 256 != 0) */
+  float* dgamma_part; float* dbeta_part; int n_part;   /* [n_part][D]; n_part <= ceil(rows / h),
+                                                          the table above */
   float* dbranch_part;     /* optional [n_part][D]: column sums of dbranch (the bias
                               gradient of the Linear that produced y) */
   const void* dout2;       /* optional dtype [rows][D], added to dout: the input gradient
@@ -263,6 +281,16 @@ typedef struct nstl_ln_args {
 } nstl_ln_args;
 int nstl_ln_fwd(const nstl_ln_args* args, void* stream);
 int nstl_ln_bwd(const nstl_ln_args* args, void* stream);
+/* The route of these arguments as text, for tests and messages: host arithmetic, the
+   snprintf convention (at most n bytes written, terminated; returns the full length).
+   Tensor pointers other than q8's are not looked at, but for the alignment above.  One of:
+     rejected: <the error text of nstl_ln_fwd / nstl_ln_bwd>
+     wave <fwd|bwd> <bf16|f32> V=2
+     wave-il <fwd|bwd> <bf16|f32> V=<4..32> G=<4|8>[ q8]        q8: the call sets q8
+     rowcoop fwd <bf16|f32> waves=<ceil(D/256)>
+     rowcoop bwd <bf16|f32> waves=<ceil(D/512)> groups=<8/waves>
+   Every token is a template argument or a launch dimension of the kernel that runs. */
+int nstl_ln_route_describe(const nstl_ln_args* args, int backward, char* buf, int n);
 
 /* out[j] = beta*out[j] + sum_p part[p][j]  (f32) */
 int nstl_reduce_rows(const float* part, int n_part, int cols, float* out, float beta, void* stream);
@@ -463,7 +491,8 @@ const char* nstl_last_error_string(void);
    6: nstl_loss_args.flags, NSTL_LOSS_WIDE_OK (the fused loss at 64 < F <= 128),
       NSTL_K_LOSS_WIDE.
    7: nstl_resample_poly, nstl_resample_out_len, nstl_peak_normalise (audio ingest on
-      the device); no struct changed. */
+      the device); no struct changed.
+   8: nstl_ln_route_describe; no struct changed. */
 int nstl_version(void);
 
 /* Launch counters by kernel family, process-wide (host side, counted at each

@@ -127,7 +127,7 @@ EXPORTS = [
     "nstl_gemm", "nstl_gemm_grouped", "nstl_gemm_colsum_rows", "nstl_gemm_relu_mask_words",
     "nstl_gemm_workspace_bytes",
     "nstl_attn_fwd", "nstl_attn_bwd", "nstl_attn_bias_rows", "nstl_attn_mask_words", "nstl_attn_route_describe",
-    "nstl_ln_fwd", "nstl_ln_bwd",
+    "nstl_ln_fwd", "nstl_ln_bwd", "nstl_ln_route_describe",
     "nstl_reduce_rows", "nstl_reduce_rows_strided", "nstl_reduce_rows3", "nstl_reduce_rows_batch",
     "nstl_colsum", "nstl_rope",
     "nstl_loss_fwd_bwd", "nstl_sumsq", "nstl_adam_step", "nstl_clip_coef", "nstl_cast", "nstl_copy2d", "nstl_autocorr",
@@ -181,6 +181,9 @@ def lib():
             L.nstl_attn_route_describe.restype = _i32
         L.nstl_ln_fwd.argtypes = [P(LnArgs), _vp]
         L.nstl_ln_bwd.argtypes = [P(LnArgs), _vp]
+        if hasattr(L, "nstl_ln_route_describe"):  # version 8
+            L.nstl_ln_route_describe.argtypes = [P(LnArgs), _i32, ctypes.c_char_p, _i32]
+            L.nstl_ln_route_describe.restype = _i32
         L.nstl_reduce_rows.argtypes = [_vp, _i32, _i32, _vp, _f32, _vp]
         L.nstl_reduce_rows_strided.argtypes = [_vp, _i64, _i32, _i32, _vp, _f32, _vp]
         L.nstl_reduce_rows3.argtypes = [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp]
@@ -540,6 +543,71 @@ def attn_fwd(a, stream=None):
 
 def attn_bwd(a, stream=None):
     check(lib().nstl_attn_bwd(ctypes.byref(a), stream if stream is not None else stream_of()), "nstl_attn_bwd")
+
+
+def ln_args(dtype, rows, D, n_masks=0, p_drop=0.0, seed1=0, seed2=0, eps=1e-5, n_part=0):
+    """The shape half of one LayerNorm call (dtype: F32 / BF16); which kernels it takes is
+    the table above nstl_ln_args in include/nstl.h, ln_route(a) names them."""
+    a = LnArgs()
+    a.dtype, a.rows, a.D = dtype, rows, D
+    a.n_masks, a.p_drop = n_masks, p_drop
+    a.seed1, a.seed2 = seed1 & 0xFFFFFFFFFFFFFFFF, seed2 & 0xFFFFFFFFFFFFFFFF
+    a.eps, a.n_part = eps, n_part
+    a.tensors = {}
+    return a
+
+
+# ln_set operands: name -> (element type: None = the call's dtype, extent, its text)
+_LN_OPS = {name: (dt, n, text) for names, dt, n, text in (
+    (("x", "y", "s_out", "out", "rot_out", "s_in", "dbranch", "dout2"), None, lambda a: a.rows * a.D, "[rows][D]"),
+    (("dout", "ds"), torch.float32, lambda a: a.rows * a.D, "[rows][D]"),
+    (("mean", "rstd", "q8_scale"), torch.float32, lambda a: a.rows, "[rows]"),
+    (("gamma", "beta"), torch.float32, lambda a: a.D, "[D]"),
+    (("rope_cos", "rope_sin"), torch.float32, lambda a: a.rope_T * (a.D // 2), "[rope_T][D/2]"),
+    (("dgamma_part", "dbeta_part", "dbranch_part"), torch.float32, lambda a: a.n_part * a.D, "[n_part][D]"),
+    (("q8",), torch.float8_e4m3fn, None, "[rows][ldq8]"),
+) for name in names}
+
+
+def ln_set(a, rope_T=None, **ops):
+    """Point the LnArgs `a` (ln_args) at tensors, each checked against the extent the call
+    addresses (ValueError) and the element type it is read as (TypeError) before anything
+    is launched: the table _LN_OPS; q8's row stride comes from the tensor, rope_T says how
+    many rows the rope tables have.  `a` keeps a reference to every tensor it points at,
+    so a temporary lives until the struct is dropped."""
+    if rope_T is not None:
+        a.rope_T = rope_T
+    for name, t in ops.items():
+        if name not in _LN_OPS:
+            raise TypeError("ln_set: unknown operand %r" % name)
+        if t is None:
+            setattr(a, name, None)
+            a.tensors.pop(name, None)
+            continue
+        dt, n, text = _LN_OPS[name]
+        if dt is None:
+            dt = torch.bfloat16 if a.dtype == BF16 else torch.float32
+        if t.dtype != dt:
+            raise TypeError("nstl_ln %s %s: a %s tensor where the call reads %s" % (name, text, t.dtype, dt))
+        if name == "q8":
+            a.ldq8 = t.stride(0)
+            _need_mat(t, a.rows, a.D, a.ldq8, "nstl_ln q8 [rows][ldq8]")
+        else:
+            _check_side(t, n(a), "nstl_ln %s %s" % (name, text))
+        setattr(a, name, t.data_ptr())
+        a.tensors[name] = t
+    return a
+
+
+def ln_route(a, backward=False):
+    """The kernel nstl_ln_fwd (backward: nstl_ln_bwd) would run for `a`, as the text of
+    nstl_ln_route_describe (include/nstl.h); host arithmetic, nothing is launched."""
+    fn = getattr(lib(), "nstl_ln_route_describe", None)
+    if fn is None:
+        raise RuntimeError("nstl_ln_route_describe: the loaded library is older than version 8")
+    buf = ctypes.create_string_buffer(160)
+    fn(ctypes.byref(a), int(backward), buf, len(buf))
+    return buf.value.decode()
 
 
 def ln_fwd(a, stream=None):

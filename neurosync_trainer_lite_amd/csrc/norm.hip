@@ -796,75 +796,104 @@ __global__ __launch_bounds__(NTR) void ln_bwd_kernel_rc(LnParams p) {
   if (p.dyp) storeG<float, CB>(p.dyp + o, dyb);
 }
 
-// forward at 1024 < D <= 2048, D % 256 == 0: V = D / 64 columns per lane, in lane
-// groups of eight columns (16-byte bf16 accesses) when D % 512 == 0, else of four
-template <typename T, int V>
-void launch_fwd_il(const LnParams& p, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((ln_fwd_kernel_il<T, V, (V % 8 == 0 ? 8 : 4)>), dim3(grid), dim3(NT), 0, st, p);
+// Host side: the one decision "which kernel does this call run?", the table above
+// nstl_ln_args in nstl.h.  The entry points and nstl_ln_route_describe read the LnRoute
+// of a call; nothing else looks at D, dtype or q8 to choose a kernel.
+// wave-il: V = D / 64 columns per lane, in lane groups of eight columns (16-byte bf16
+// accesses) when D % 512 == 0, else of four; up to the V that still fits the registers
+constexpr int IL_MAX_V_FWD = 32, IL_MAX_V_BWD = 16;
+constexpr int il_group(int V) { return V % 8 == 0 ? 8 : 4; }
+static_assert(NTR == 512, "RC_PART_LDS is sized for at most 8 row groups");
+
+struct LnRoute {
+  enum Family { REJECTED, WAVE, WAVE_IL, ROWCOOP } family;
+  bool bf16, q8;
+  int V, G;            // WAVE: ln_*_kernel<T, V>; WAVE_IL: ln_*_kernel_il<T, V, G>
+  int waves, groups;   // ROWCOOP: ln_*_kernel_rc<T>, waves per row and row groups per block
+  int block, grid;     // the launch
+  int rows_per_block;  // forward: grid = ceil(rows / it); backward: n_part <= ceil(rows / it)
+  char why[128];       // REJECTED: the error text of the entry points
+};
+
+// Validates the shape half of the arguments (the null-pointer checks on tensors are the
+// entry points' and fill()'s) and routes them.
+LnRoute ln_route(const nstl_ln_args* a, bool bwd) {
+  LnRoute r = {};
+  r.family = LnRoute::REJECTED;
+  const char* fn = bwd ? "nstl_ln_bwd" : "nstl_ln_fwd";
+#define NSTL_ROUTE_CHECK(cond, ...) \
+  if (!(cond)) return snprintf(r.why, sizeof(r.why), __VA_ARGS__), r
+  NSTL_ROUTE_CHECK(a != nullptr, "nstl_ln: null args");
+  NSTL_ROUTE_CHECK(a->dtype == NSTL_F32 || a->dtype == NSTL_BF16, "nstl_ln: bad dtype");
+  NSTL_ROUTE_CHECK(a->rows > 0, "nstl_ln: bad shape (rows=%d)", a->rows);
+  const int D = a->D, V = D / 64;
+  NSTL_ROUTE_CHECK(D >= 128 && D % 128 == 0 && D <= 2048,
+                   "nstl_ln: D=%d unsupported (a multiple of 128, 128 <= D <= 2048)", D);
+  r.bf16 = a->dtype == NSTL_BF16;
+  r.q8 = a->q8 != nullptr;
+  NSTL_ROUTE_CHECK(!r.q8 || D == 256 || D == 512 || D == 1024,
+                   "nstl_ln: the q8 / q8_scale copy (fp8) needs D in 256/512/1024 (got %d)", D);
+  NSTL_ROUTE_CHECK(a->n_masks >= 0 && a->n_masks <= 2 && a->p_drop >= 0.f && a->p_drop < 1.f, "nstl_ln: dropout");
+  NSTL_ROUTE_CHECK(a->p_drop == 0.f || nstl_pair_index32_ok((uint64_t)a->rows * D),
+                   "nstl_ln: rows*D past 2^33 dropout elements (32-bit pair index)");
+  NSTL_ROUTE_CHECK(!r.q8 || (r.bf16 && a->q8_scale && (!bwd || a->dbranch) && a->ldq8 >= D && a->ldq8 % 16 == 0 &&
+                             (uintptr_t)a->q8 % 16 == 0),
+                   "%s: q8 needs %sbf16, q8_scale and a 16-byte aligned ldq8 >= D", fn, bwd ? "dbranch, " : "");
+  const bool wave = V == 2, il = D % 256 == 0 && V <= (bwd ? IL_MAX_V_BWD : IL_MAX_V_FWD);
+  r.rows_per_block = bwd ? (D % 256 == 0 ? NTB / 64 : NT / 64) : (wave || il ? NT / 64 : RCF);
+  r.grid = (a->rows + r.rows_per_block - 1) / r.rows_per_block;
+  if (bwd) {  // n_part blocks, each with at least one row per wave
+    NSTL_ROUTE_CHECK(a->n_part > 0, "nstl_ln_bwd: partials");
+    NSTL_ROUTE_CHECK(a->n_part <= r.grid, "nstl_ln_bwd: n_part (%d) must be <= rows/%d", a->n_part, r.rows_per_block);
+    r.grid = a->n_part;
+  }
+  // the widths at which a direction runs row-cooperative (their float4 / float2 table reads)
+  NSTL_ROUTE_CHECK(wave || (D % 256 == 0 && V <= IL_MAX_V_BWD) ||
+                       (((uintptr_t)a->gamma | (uintptr_t)a->beta) % 16 == 0 &&
+                        ((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin) % 8 == 0),
+                   "nstl_ln: D=%d needs 16-byte aligned gamma/beta and 8-byte aligned rope tables", D);
+#undef NSTL_ROUTE_CHECK
+  if (wave || il) {
+    r.family = wave ? LnRoute::WAVE : LnRoute::WAVE_IL;
+    r.V = V;
+    r.G = wave ? 0 : il_group(V);
+    r.block = wave || !bwd ? NT : NTB;
+  } else {
+    r.family = LnRoute::ROWCOOP;  // forward: 4 columns per thread; backward: CB, in 8 / waves row groups
+    r.waves = bwd ? (D + 64 * CB - 1) / (64 * CB) : (D + 255) / 256;
+    r.groups = bwd ? NTR / 64 / r.waves : 1;
+    r.block = r.groups * r.waves * 64;
+  }
+  return r;
 }
 
+// p filled from the arguments r routed; exactly the reachable kernels are instantiated
 template <typename T, bool BWD>
-int dispatch(const LnParams& p, int grid, hipStream_t st) {
-#define NSTL_LN_CASE(V)                                                                     \
-  case V:                                                                                   \
-    if (BWD && V % 8 == 0)                                                                  \
-      hipLaunchKernelGGL((ln_bwd_kernel_il<T, (V % 8 == 0 ? V : 8), 8>), dim3(grid), dim3(NTB), 0, st, p); \
-    else if (BWD && V % 4 == 0)                                                             \
-      hipLaunchKernelGGL((ln_bwd_kernel_il<T, (V % 8 == 4 ? V : 4), 4>), dim3(grid), dim3(NTB), 0, st, p); \
-    else if (BWD) hipLaunchKernelGGL((ln_bwd_kernel<T, V>), dim3(grid), dim3(NT), 0, st, p); \
-    else if (V % 8 == 0)                                                                    \
-      hipLaunchKernelGGL((ln_fwd_kernel_il<T, (V % 8 == 0 ? V : 8), 8>), dim3(grid), dim3(NT), 0, st, p); \
-    else if (V % 4 == 0)                                                                    \
-      hipLaunchKernelGGL((ln_fwd_kernel_il<T, (V % 8 == 4 ? V : 4), 4>), dim3(grid), dim3(NT), 0, st, p); \
-    else hipLaunchKernelGGL((ln_fwd_kernel<T, V>), dim3(grid), dim3(NT), 0, st, p);        \
-    break;
-  switch (p.D / 64) {
-    NSTL_LN_CASE(2)
-    NSTL_LN_CASE(4)
-    NSTL_LN_CASE(8)
-    NSTL_LN_CASE(12)
-    NSTL_LN_CASE(16)
-    default: {
-      // row-cooperative kernels: a block per RCF rows (forward) / per partial (backward)
-      if (p.D % 128 || p.D > 2048)
-        return nstl::fail((int)hipErrorInvalidValue,
-                          "nstl_ln: D=%d unsupported (a multiple of 128, 128 <= D <= 2048)", p.D);
-      if (((uintptr_t)p.gamma | (uintptr_t)p.beta) % 16 || ((uintptr_t)p.rope_cos | (uintptr_t)p.rope_sin) % 8)
-        return nstl::fail((int)hipErrorInvalidValue,
-                          "nstl_ln: D=%d needs 16-byte aligned gamma/beta and 8-byte aligned rope tables", p.D);
-      if (!BWD && p.D % 256 == 0) {  // the forward's wave-per-row kernel still fits its registers
-        switch (p.D / 64) {
-          case 20: launch_fwd_il<T, 20>(p, grid, st); break;
-          case 24: launch_fwd_il<T, 24>(p, grid, st); break;
-          case 28: launch_fwd_il<T, 28>(p, grid, st); break;
-          default: launch_fwd_il<T, 32>(p, grid, st); break;
-        }
-        break;
-      }
-      static_assert(NTR == 512, "RC_PART_LDS is sized for at most 8 row groups");
-      const int wpr = (p.D + 255) / 256;                                   // forward: 4 columns per thread
-      const int wprb = (p.D + 64 * CB - 1) / (64 * CB), ng = NTR / 64 / wprb;  // backward: 8
-      if (BWD) hipLaunchKernelGGL((ln_bwd_kernel_rc<T>), dim3(grid), dim3(ng * wprb * 64), 0, st, p);
-      else hipLaunchKernelGGL((ln_fwd_kernel_rc<T>), dim3((p.rows + RCF - 1) / RCF), dim3(wpr * 64), 0, st, p);
-    }
+int launch(const LnParams& p, const LnRoute& r, hipStream_t st) {
+  const dim3 grid(r.grid), block(r.block);
+  bool found = true;
+  if (r.family == LnRoute::WAVE) {
+    if constexpr (BWD) hipLaunchKernelGGL((ln_bwd_kernel<T, 2>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((ln_fwd_kernel<T, 2>), grid, block, 0, st, p);
+  } else if (r.family == LnRoute::ROWCOOP) {
+    if constexpr (BWD) hipLaunchKernelGGL((ln_bwd_kernel_rc<T>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((ln_fwd_kernel_rc<T>), grid, block, 0, st, p);
+  } else if constexpr (BWD) {
+    found = nstl::with_const<4, 8, 12, IL_MAX_V_BWD>(r.V, [&](auto V) {
+      hipLaunchKernelGGL((ln_bwd_kernel_il<T, V(), il_group(V())>), grid, block, 0, st, p);
+    });
+  } else {
+    found = nstl::with_const<4, 8, 12, 16, 20, 24, 28, IL_MAX_V_FWD>(r.V, [&](auto V) {
+      hipLaunchKernelGGL((ln_fwd_kernel_il<T, V(), il_group(V())>), grid, block, 0, st, p);
+    });
   }
-#undef NSTL_LN_CASE
+  if (!found) return nstl::fail((int)hipErrorInvalidValue, "nstl_ln: no kernel for D=%d", p.D);
   NSTL_LAUNCH_CHECK(BWD ? "nstl_ln_bwd" : "nstl_ln_fwd");
   return 0;
 }
 
 int fill(LnParams& p, const nstl_ln_args* a) {
-  NSTL_CHECK_ARG(a != nullptr, "nstl_ln: null args");
-  NSTL_CHECK_ARG(a->dtype == NSTL_F32 || a->dtype == NSTL_BF16, "nstl_ln: bad dtype");
-  NSTL_CHECK_ARG(a->rows > 0, "nstl_ln: bad shape (rows=%d)", a->rows);
-  NSTL_CHECK_ARG(a->D >= 128 && a->D % 128 == 0 && a->D <= 2048,
-                 "nstl_ln: D=%d unsupported (a multiple of 128, 128 <= D <= 2048)", a->D);
-  NSTL_CHECK_ARG(!a->q8 || a->D == 128 || a->D == 256 || a->D == 512 || a->D == 1024,
-                 "nstl_ln: the q8 / q8_scale copy (fp8) needs D in 128/256/512/1024 (got %d)", a->D);
   NSTL_CHECK_ARG(a->gamma && a->beta, "nstl_ln: gamma/beta missing");
-  NSTL_CHECK_ARG(a->n_masks >= 0 && a->n_masks <= 2 && a->p_drop >= 0.f && a->p_drop < 1.f, "nstl_ln: dropout");
-  NSTL_CHECK_ARG(a->p_drop == 0.f || nstl_pair_index32_ok((uint64_t)a->rows * a->D),
-                 "nstl_ln: rows*D past 2^33 dropout elements (32-bit pair index)");
   p.x = (const char*)a->x; p.y = (const char*)a->y;
   p.rows = a->rows; p.D = a->D;
   p.n_masks = a->n_masks;
@@ -884,32 +913,38 @@ int fill(LnParams& p, const nstl_ln_args* a) {
 }  // namespace
 
 extern "C" int nstl_ln_fwd(const nstl_ln_args* a, void* stream) {
+  const LnRoute r = ln_route(a, false);
+  if (r.family == LnRoute::REJECTED) return nstl::fail((int)hipErrorInvalidValue, "%s", r.why);
+  NSTL_CHECK_ARG(a->y && a->out && a->mean && a->rstd, "nstl_ln_fwd: null tensor");
+  NSTL_CHECK_ARG(!a->rot_out || (a->rope_cos && a->rope_sin && a->rope_T > 0), "nstl_ln_fwd: rope tables");
   LnParams p;
   int rc = fill(p, a);
   if (rc) return rc;
-  NSTL_CHECK_ARG(a->y && a->out && a->mean && a->rstd, "nstl_ln_fwd: null tensor");
-  NSTL_CHECK_ARG(!a->rot_out || (a->rope_cos && a->rope_sin && a->rope_T > 0), "nstl_ln_fwd: rope tables");
-  NSTL_CHECK_ARG(!a->q8 || (a->dtype == NSTL_BF16 && a->q8_scale && a->D % 256 == 0 && a->ldq8 >= a->D &&
-                            a->ldq8 % 16 == 0 && ((uintptr_t)a->q8 % 16) == 0),
-                 "nstl_ln_fwd: q8 needs bf16, D %% 256 == 0, q8_scale and a 16-byte aligned ldq8 >= D");
-  const int grid = (a->rows + NT / 64 - 1) / (NT / 64);
-  return a->dtype == NSTL_BF16 ? dispatch<bf16, false>(p, grid, (hipStream_t)stream)
-                               : dispatch<float, false>(p, grid, (hipStream_t)stream);
+  return r.bf16 ? launch<bf16, false>(p, r, (hipStream_t)stream) : launch<float, false>(p, r, (hipStream_t)stream);
 }
 
 extern "C" int nstl_ln_bwd(const nstl_ln_args* a, void* stream) {
+  const LnRoute r = ln_route(a, true);
+  if (r.family == LnRoute::REJECTED) return nstl::fail((int)hipErrorInvalidValue, "%s", r.why);
+  NSTL_CHECK_ARG(a->s_in && a->dout && a->ds && a->mean && a->rstd, "nstl_ln_bwd: null tensor");
+  NSTL_CHECK_ARG(a->dgamma_part && a->dbeta_part, "nstl_ln_bwd: partials");
   LnParams p;
   int rc = fill(p, a);
   if (rc) return rc;
-  NSTL_CHECK_ARG(a->s_in && a->dout && a->ds && a->mean && a->rstd, "nstl_ln_bwd: null tensor");
-  NSTL_CHECK_ARG(a->dgamma_part && a->dbeta_part && a->n_part > 0, "nstl_ln_bwd: partials");
-  NSTL_CHECK_ARG(!a->q8 || (a->dbranch && a->dtype == NSTL_BF16 && a->q8_scale && a->D % 256 == 0 &&
-                            a->ldq8 >= a->D && a->ldq8 % 16 == 0 && ((uintptr_t)a->q8 % 16) == 0),
-                 "nstl_ln_bwd: q8 needs dbranch, bf16, D %% 256 == 0, q8_scale and a 16-byte aligned ldq8 >= D");
-  // n_part blocks; each needs at least one row per wave (4 waves; 8 when D % 256 == 0)
-  const int nw = (a->D % 256 == 0) ? NTB / 64 : NT / 64;
-  const int grid = std::min(a->n_part, (a->rows + nw - 1) / nw);
-  NSTL_CHECK_ARG(grid == a->n_part, "nstl_ln_bwd: n_part (%d) must be <= rows/%d", a->n_part, nw);
-  return a->dtype == NSTL_BF16 ? dispatch<bf16, true>(p, grid, (hipStream_t)stream)
-                               : dispatch<float, true>(p, grid, (hipStream_t)stream);
+  return r.bf16 ? launch<bf16, true>(p, r, (hipStream_t)stream) : launch<float, true>(p, r, (hipStream_t)stream);
+}
+
+extern "C" int nstl_ln_route_describe(const nstl_ln_args* a, int backward, char* buf, int n) {
+  const LnRoute r = ln_route(a, backward != 0);
+  const size_t cap = buf && n > 0 ? (size_t)n : 0;
+  const char *dir = backward ? "bwd" : "fwd", *ty = r.bf16 ? "bf16" : "f32";
+  switch (r.family) {
+    case LnRoute::REJECTED: return snprintf(buf, cap, "rejected: %s", r.why);
+    case LnRoute::WAVE: return snprintf(buf, cap, "wave %s %s V=%d", dir, ty, r.V);
+    case LnRoute::WAVE_IL: return snprintf(buf, cap, "wave-il %s %s V=%d G=%d%s", dir, ty, r.V, r.G, r.q8 ? " q8" : "");
+    case LnRoute::ROWCOOP:
+      return backward ? snprintf(buf, cap, "rowcoop bwd %s waves=%d groups=%d", ty, r.waves, r.groups)
+                      : snprintf(buf, cap, "rowcoop fwd %s waves=%d", ty, r.waves);
+  }
+  return -1;
 }

@@ -127,4 +127,5 @@ extern "C" const char* nstl_last_error_string(void) { return nstl::g_last_error.
 // 2: nstl_attn_args gained `flags` (a struct of the ABI changed size)
 // 6: nstl_loss_args gained `flags` likewise (NSTL_LOSS_WIDE_OK)
 // 7: nstl_resample_poly / nstl_resample_out_len / nstl_peak_normalise (csrc/resample.hip)
-extern "C" int nstl_version(void) { return 7; }
+// 8: nstl_ln_route_describe (csrc/norm.hip)
+extern "C" int nstl_version(void) { return 8; }

@@ -54,7 +54,8 @@ def _pad64(n):
 
 
 # the LayerNorm kernels write the e4m3 side copies (nstl_ln_args.q8) at these widths only
-FP8_WIDTHS = (128, 256, 512, 1024)
+# (the table above nstl_ln_args in include/nstl.h; tests/test_ln_route_cpu.py holds the two together)
+FP8_WIDTHS = (256, 512, 1024)
 
 
 def fp8_width_error(D):
@@ -199,6 +200,7 @@ class Seq2SeqEngine:
         self._check_shapes()
         self._build_arena()
         self._bufs = {}
+        self._ln_calls = {}        # _ln_call: the validated LnArgs of the live workspaces
         self._rope = {}
         self.generation = 0
         self.grads_fresh = True
@@ -530,6 +532,7 @@ class Seq2SeqEngine:
             if save:  # keep at most one training workspace alive
                 for k2 in [k for k in self._bufs if k[2]]:
                     del self._bufs[k2]
+            self._ln_calls.clear()
             self._bufs[key] = _Buffers(self, B, T, save)
         return self._bufs[key]
 
@@ -830,23 +833,31 @@ class Seq2SeqEngine:
         else:
             self._dx(dy, wname, rows, bb.dres, 1.0)
 
+    def _ln_call(self, ops, rows, n_masks, seeds, n_part=0, rope_T=0):
+        """The filled LnArgs of one LayerNorm call.  K.ln_set checks every operand's extent;
+        a given (buffers, shape) is checked once and its struct, which holds the tensors, is
+        reused with the step's seeds while the same buffers come back (bufs() drops the
+        structs with the workspace it evicts).  A call with an e4m3 copy is filled every
+        time: those buffers are reallocated when the row count changes."""
+        key = (rows, n_masks, self.p, n_part, rope_T) + tuple((k, t.data_ptr()) for k, t in ops.items() if t is not None)
+        a = self._ln_calls.get(key)
+        if a is None:
+            a = K.ln_set(K.ln_args(K.dtype_code(self.dt), rows, self.D, n_masks, self.p, n_part=n_part), rope_T=rope_T, **ops)
+            if "q8" not in ops:
+                self._ln_calls[key] = a
+        a.seed1, a.seed2 = seeds
+        return a
+
     def _ln(self, x, y, out, stats, prefix, n_masks, seeds, s_out, rot=None, T=None, q8=None):
         """LayerNorm tail; in fp8 mode (q8 = 'scratch' / 'mem') it also writes the
         row-wise e4m3 copy of `out` that the next fp8 projection reads."""
-        a = K.LnArgs()
-        a.dtype = K.dtype_code(self.dt)
-        a.rows, a.D = out.shape[0], self.D
-        a.x, a.y = K.ptr(x), K.ptr(y)
-        a.n_masks, a.p_drop = n_masks, self.p
-        a.seed1, a.seed2 = seeds
-        a.gamma, a.beta, a.eps = self.b(prefix + ".weight").data_ptr(), self.b(prefix + ".bias").data_ptr(), 1e-5
-        a.s_out, a.out, a.mean, a.rstd = K.ptr(s_out), out.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr()
+        ops = dict(x=x, y=y, gamma=self.b(prefix + ".weight"), beta=self.b(prefix + ".bias"), s_out=s_out, out=out,
+                   mean=stats[0], rstd=stats[1])
         if rot is not None:
-            cs, sn = self.rope(T, self.D)
-            a.rot_out, a.rope_cos, a.rope_sin, a.rope_T = rot.data_ptr(), cs.data_ptr(), sn.data_ptr(), T
+            ops["rot_out"], (ops["rope_cos"], ops["rope_sin"]) = rot, self.rope(T, self.D)
         if self.fp8 and q8 is not None:
-            q, sc = self._fp8_target(out, q8 == "mem")
-            a.q8, a.ldq8, a.q8_scale = q.data_ptr(), q.stride(0), sc.data_ptr()
+            ops["q8"], ops["q8_scale"] = q, sc = self._fp8_target(out, q8 == "mem")
+        a = self._ln_call(ops, out.shape[0], n_masks, seeds, rope_T=T if rot is not None else 0)
         K.ln_fwd(a, stream=self.st)
         if self.fp8 and q8 is not None:
             self._xq[out.data_ptr()] = (q, sc)
@@ -856,26 +867,17 @@ class Seq2SeqEngine:
         dbranch become grad(bias) of that Linear (its output was the LN branch);
         `q8` = (e4m3 [rows, D], scales [rows]): also the row-wise e4m3 copy of dbranch."""
         bb = self.cur
-        a = K.LnArgs()
-        a.dtype = K.dtype_code(self.dt)
-        a.rows, a.D = s_in.shape[0], self.D
-        a.n_masks, a.p_drop = n_masks, self.p
-        a.seed1, a.seed2 = seeds
-        a.gamma, a.beta, a.eps = self.b(prefix + ".weight").data_ptr(), self.b(prefix + ".bias").data_ptr(), 1e-5
-        a.mean, a.rstd = stats[0].data_ptr(), stats[1].data_ptr()
-        a.s_in, a.dout, a.ds, a.dbranch = s_in.data_ptr(), dres_in.data_ptr(), dres_out.data_ptr(), K.ptr(dbranch)
-        if self._dadd_pending:
-            a.dout2 = bb.dadd.data_ptr()
-            self._dadd_pending = False
         part = bb.ln_part
         if self._red is not None:
             part = bb.ln_parts[self._ln_slot]
             self._ln_slot += 1
-        a.dgamma_part, a.dbeta_part, a.n_part = part[0].data_ptr(), part[1].data_ptr(), bb.n_part
-        if bias_of is not None:
-            a.dbranch_part = part[2].data_ptr()
+        ops = dict(gamma=self.b(prefix + ".weight"), beta=self.b(prefix + ".bias"), mean=stats[0], rstd=stats[1],
+                   s_in=s_in, dout=dres_in, ds=dres_out, dbranch=dbranch, dgamma_part=part[0], dbeta_part=part[1],
+                   dout2=bb.dadd if self._dadd_pending else None, dbranch_part=part[2] if bias_of is not None else None)
+        self._dadd_pending = False
         if q8 is not None:
-            a.q8, a.ldq8, a.q8_scale = q8[0].data_ptr(), q8[0].stride(0), q8[1].data_ptr()
+            ops["q8"], ops["q8_scale"] = q8
+        a = self._ln_call(ops, s_in.shape[0], n_masks, seeds, n_part=bb.n_part)
         K.ln_bwd(a, stream=self.st)
         outs = [self.gb(prefix + ".weight"), self.gb(prefix + ".bias")]
         if bias_of is not None:

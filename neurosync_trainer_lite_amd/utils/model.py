@@ -78,13 +78,9 @@ def _layer_norm_f32(ln, x2, y2):
     out = torch.empty_like(x2)
     mean = torch.empty(M, dtype=torch.float32, device=x2.device)
     rstd = torch.empty_like(mean)
-    a = K.LnArgs()
-    a.dtype, a.rows, a.D = K.F32, M, D
-    a.x, a.y = x2.data_ptr(), y2.data_ptr()
-    a.n_masks, a.p_drop = 0, 0.0
-    a.gamma, a.beta, a.eps = (ln.weight.detach().float().contiguous().data_ptr(),
-                              ln.bias.detach().float().contiguous().data_ptr(), ln.eps)
-    a.out, a.mean, a.rstd = out.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+    a = K.ln_args(K.F32, M, D, eps=ln.eps)
+    K.ln_set(a, x=x2, y=y2, gamma=ln.weight.detach().float().contiguous(), beta=ln.bias.detach().float().contiguous(),
+             out=out, mean=mean, rstd=rstd)
     K.ln_fwd(a)
     return out
 

@@ -1,6 +1,6 @@
 """The host-side width rules that need no device: hidden_dim is a multiple of 128 up
 to 2048 (Seq2SeqEngine._check_shapes runs ahead of any device work), and fp8
-projections stay with hidden_dim in 128 / 256 / 512 / 1024 (the LayerNorm kernels
+projections stay with hidden_dim in 256 / 512 / 1024 (the LayerNorm kernels
 write the e4m3 side copies at those widths only)."""
 import pytest
 import torch
@@ -32,7 +32,7 @@ def test_new_widths_pass_the_shape_check(D, H):
 
 def test_fp8_at_768_is_refused():
     m = model(768, 12)
-    with pytest.raises(ValueError, match=r"fp8 projections need hidden_dim in \(128, 256, 512, 1024\) \(got 768\)"):
+    with pytest.raises(ValueError, match=r"fp8 projections need hidden_dim in \(256, 512, 1024\) \(got 768\)"):
         m.set_fp8(True)
     assert not m.fp8
     with pytest.raises(ValueError, match="fp8 projections need hidden_dim"):

@@ -38,26 +38,16 @@ class Arm:
         self.bytes = {"fwd": R * D * 2 * 4, "bwd": R * D * 14}
         self.times = {"fwd": [], "bwd": []}
 
-    def args(self, n_masks):
-        a = K.LnArgs()
-        a.dtype, a.rows, a.D = K.dtype_code(bf), self.R, self.D
-        a.n_masks, a.p_drop, a.seed1, a.seed2 = n_masks, 0.3, 11, 12
-        a.gamma, a.beta, a.eps = self.gamma.data_ptr(), self.beta.data_ptr(), 1e-5
-        a.mean, a.rstd = self.stat[0].data_ptr(), self.stat[1].data_ptr()
-        return a
+    def args(self, n_masks, **ops):
+        a = K.ln_args(K.dtype_code(bf), self.R, self.D, n_masks, 0.3, 11, 12, n_part=N_PART)
+        return K.ln_set(a, gamma=self.gamma, beta=self.beta, mean=self.stat[0], rstd=self.stat[1], **ops)
 
     def fwd(self):
-        a = self.args(1)
-        a.x, a.y, a.s_out, a.out = self.x.data_ptr(), self.y.data_ptr(), self.s.data_ptr(), self.out.data_ptr()
-        K.ln_fwd(a)
+        K.ln_fwd(self.args(1, x=self.x, y=self.y, s_out=self.s, out=self.out))
 
     def bwd(self):
-        a = self.args(2)
-        a.s_in, a.dout, a.ds, a.dbranch = self.s.data_ptr(), self.dres.data_ptr(), self.dres.data_ptr(), self.dbranch.data_ptr()
-        a.dout2 = self.dadd.data_ptr()
-        a.dgamma_part, a.dbeta_part, a.n_part = self.part[0].data_ptr(), self.part[1].data_ptr(), N_PART
-        a.dbranch_part = self.part[2].data_ptr()
-        K.ln_bwd(a)
+        K.ln_bwd(self.args(2, s_in=self.s, dout=self.dres, ds=self.dres, dbranch=self.dbranch, dout2=self.dadd,
+                           dgamma_part=self.part[0], dbeta_part=self.part[1], dbranch_part=self.part[2]))
 
 
 def timed(fn):

@@ -45,13 +45,8 @@ beta = torch.zeros(D, device=dev)
 
 
 def ln_fwd(n_masks=1):
-    a = K.LnArgs()
-    a.dtype, a.rows, a.D = K.dtype_code(bf), R, D
-    a.x, a.y = x.data_ptr(), y.data_ptr()
-    a.n_masks, a.p_drop, a.seed1, a.seed2 = n_masks, 0.3 if n_masks else 0.0, 11, 12
-    a.gamma, a.beta, a.eps = gamma.data_ptr(), beta.data_ptr(), 1e-5
-    a.s_out, a.out, a.mean, a.rstd = s_out.data_ptr(), out.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-    K.ln_fwd(a)
+    a = K.ln_args(K.dtype_code(bf), R, D, n_masks, 0.3 if n_masks else 0.0, 11, 12)
+    K.ln_fwd(K.ln_set(a, x=x, y=y, gamma=gamma, beta=beta, s_out=s_out, out=out, mean=mean, rstd=rstd))
 
 
 dres = torch.randn(R, D, device=dev) * 1e-3
@@ -62,16 +57,9 @@ torch.cuda.synchronize()
 
 
 def ln_bwd(n_part, part, n_masks=2):
-    a = K.LnArgs()
-    a.dtype, a.rows, a.D = K.dtype_code(bf), R, D
-    a.n_masks, a.p_drop, a.seed1, a.seed2 = n_masks, 0.3 if n_masks else 0.0, 11, 12
-    a.gamma, a.beta, a.eps = gamma.data_ptr(), beta.data_ptr(), 1e-5
-    a.mean, a.rstd = mean.data_ptr(), rstd.data_ptr()
-    a.s_in, a.dout, a.ds, a.dbranch = s_out.data_ptr(), dres.data_ptr(), dres.data_ptr(), dbranch.data_ptr()
-    a.dout2 = dadd.data_ptr()
-    a.dgamma_part, a.dbeta_part, a.n_part = part[0].data_ptr(), part[1].data_ptr(), n_part
-    a.dbranch_part = part[2].data_ptr()
-    K.ln_bwd(a)
+    a = K.ln_args(K.dtype_code(bf), R, D, n_masks, 0.3 if n_masks else 0.0, 11, 12, n_part=n_part)
+    K.ln_bwd(K.ln_set(a, gamma=gamma, beta=beta, mean=mean, rstd=rstd, s_in=s_out, dout=dres, ds=dres, dbranch=dbranch,
+                      dout2=dadd, dgamma_part=part[0], dbeta_part=part[1], dbranch_part=part[2]))
 
 
 parts = [int(v) for v in sys.argv[1:]] or [256]
